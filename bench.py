@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: interpolation-frames/sec (50-step) of the AID attention stack on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|sd15|seq16|ip] [--early ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sdxl|sd15|seq16|ip] [--early ...] [--dump-outputs DIR] [--full]
 
 One "step" = one denoising step of the interpolation run = the ordered attention calls of one UNet
 forward (SD1.5 32 calls, SDXL 140 calls) executed twice: the conditional pass (AID
@@ -12,7 +12,7 @@ unconditional pass (plain), exactly as the reference loop toggles them
 
 Workloads (BASELINE.json configs):
   sdxl   configs[2]  SDXL 1024x1024, 7-frame PAID (guide prompt) fused-outer, bf16          <- default at --gpus 1
-  sd15   configs[1]  SD1.5 512x512, 7-frame fused-inner AID, fp16   (also reported under "also" by the default run)
+  sd15   configs[1]  SD1.5 512x512, 7-frame fused-inner AID, fp16   (also reported under "also" by --full)
   seq16  configs[3]  SDXL 1024x1024, ONE 16-frame sequence sharded by frame over the ranks  <- default at --gpus N > 1
   ip     configs[4]  SDXL + IP-Adapter image-conditioned morphing, 8-frame outer-IP, image-embed cross-attention
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks
@@ -20,12 +20,18 @@ Workloads (BASELINE.json configs):
 frame with replicated end points (dist.py): zero per-layer communication, one broadcast of the conditioning before and
 one all_gather of the owned outputs after the steps (inside the timed region).  `--weak` keeps 7 owned frames per GPU.
 
-The timed region is EXACTLY K steps, repeated `repeats` times back to back when K steps take less than a second
-(ms_per_step is the mean over K * repeats steps).  Rank 0 prints ONE JSON line; N = 1 additionally measures
+The timed region is EXACTLY K steps (ms_per_step is their mean; `--min-seconds S` repeats the K steps back to back until the
+region is S seconds long, ms_per_step then being the mean over K * repeats steps).  Rank 0 prints ONE JSON line.  A plain run
+does only that: set-up, W warm-up steps, the K timed steps, the result line.  `--dump-outputs DIR` then writes what the last
+timed step returned (the CFG-combined output of every resolution level, all frames) as DIR/<name>.npy in float32, at most
+64 MB in all (a fixed seeded sample of every level when the whole set is larger); the inputs are seeded, so two builds can be
+compared output for output.  `--full` adds the secondary measurements (each skippable by its --no-* option):
   roofline     — HIP-event timing of every kernel launch of one AID step + one plain step (aid_profile_begin/end in the
                  C ABI): algorithmic AND executed TFLOP/s per kernel symbol, the dominant symbol reported on top
-  cpu_baseline — the threaded CPU port of the path (oracle/aid_cpu_port.py, "port") timed on the host cores on a bounded
-                 sample and extrapolated to the same 50-step unit.
+  cpu_baseline — N = 1: the threaded CPU port of the path (oracle/aid_cpu_port.py, "port") timed on the host cores on a bounded
+                 sample and extrapolated to the same 50-step unit
+  also         — N = 1, the default workload: the other BASELINE configs, precisions and pass layouts, timed like the headline
+                 (these repeat their K steps up to 1 s unless --min-seconds is given), and `chained`.
 """
 import argparse
 import json
@@ -67,7 +73,9 @@ def parse():
     ap.add_argument("--weak", action="store_true", help="N > 1: 7 owned frames per GPU (7 N frames) instead of configs[3]")
     ap.add_argument("--frames-per-gpu", type=int, default=7, help="--weak: owned frames per GPU")
     ap.add_argument("--warmup-ratio", type=float, default=0.5)
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the K steps until the timed region is this long")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the K steps until the timed region is this long (default: exactly K timed steps; the --full "
+                         "secondary measurements: 1 s)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying hipGraphs")
     ap.add_argument("--passes", default="auto", choices=["auto", "batched", "streams", "serial"],
                     help="the cond and the uncond pass of a step: ONE UNet call over [cond ; uncond] (batched; how stock diffusers "
@@ -85,7 +93,7 @@ def parse():
                          "residual add behind it, as three steps (torch LayerNorm / call / torch add) or as ONE library call")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements of the default run")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary workloads of the default run")
     ap.add_argument("--no-text-kv-cache", action="store_true",
                     help="project the text keys / values in every cross-attention call like the reference does (default: "
                          "once per layer and context; the contexts do not change over the steps)")
@@ -95,6 +103,10 @@ def parse():
                     help="N > 1 layouts (SURVEY §8e / §8f.4): every rank recomputes the two end-point frames (no per-layer collective) | "
                          "ranks run their owned frames only and the owners broadcast the end points' keys / values per self-attention "
                          "layer on a side stream (eager launches, no fused sublayers)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: roofline, cpu_baseline, the `also` workloads and `chained`")
     return ap.parse_args()
 
 
@@ -207,7 +219,7 @@ _CEILING = {}
 def power_limited_peak():
     """The dense-MFMA rate THIS box sustains on random operands (tools/ubench/mfma_ceiling: four waves per CU issuing v_mfma_f32_32x32x16
     back to back from registers, nothing else — 32.0 cycles per MFMA and SIMD whatever the data, but the clock the power budget allows
-    drops from ~2.3 GHz on zeros to ~1.6 GHz on random sign / mantissa / exponent bits).  Measured once per bench run, outside every
+    drops from ~2.3 GHz on zeros to ~1.6 GHz on random sign / mantissa / exponent bits).  Measured once per --full run, outside every
     timed region; None when the helper binary is absent (python -c 'import __graft_entry__ as g; g.build()' builds it)."""
     if "v" not in _CEILING:
         _CEILING["v"] = None
@@ -463,7 +475,7 @@ def time_workload(wl, args, world, device, torch, dist):
     run_steps(warm_idx[2:] or warm_idx[:2])
     torch.cuda.synchronize()
     est = (time.perf_counter() - t0) / max(len(warm_idx[2:] or warm_idx[:2]), 1)
-    reps = max(1, int(math.ceil(args.min_seconds / max(est * steps, 1e-6))))
+    reps = max(1, int(math.ceil((args.min_seconds or 0.0) / max(est * steps, 1e-6))))
     if world > 1:
         r = torch.tensor([reps], device="cpu" if one_dev else device, dtype=torch.int64)
         dist.all_reduce(r, op=dist.ReduceOp.MAX)
@@ -487,7 +499,29 @@ def time_workload(wl, args, world, device, torch, dist):
     assert final.shape[0] == wl["n_total"] and torch.isfinite(final.float()).all()
     ms_per_step = elapsed * 1000.0 / (steps * reps)
     return dict(ms_per_step=ms_per_step, value=wl["n_total"] / (ms_per_step * 50.0 / 1000.0), repeats=reps,
-                timed_seconds=elapsed, warmup=len(warm_idx))
+                timed_seconds=elapsed, warmup=len(warm_idx), outputs=out)
+
+
+DUMP_BYTES = 60 << 20          # the .npy files of --dump-outputs stay under 64 MB together (headers included)
+
+
+def dump_outputs(outputs, shard, directory, rank):
+    """--dump-outputs: what the last timed step returned — the CFG-combined output [N, S, C] of every resolution level, the owned
+    frames of every rank gathered — as DIR/out_s<S>_c<C>.npy in float32.  When the whole set exceeds DUMP_BYTES every level keeps
+    the same fraction of its elements: a sample at sorted flat indices drawn without replacement by a generator seeded with
+    S * C, so runs with the same arguments write the same positions.  Collective over the ranks; rank 0 writes."""
+    import numpy as np
+    from aid_amd import dist as adist
+    arrays = {(s, c): adist.gather_owned(v, shard).float().cpu().numpy() for (s, c), v in outputs.items()}
+    if rank != 0:
+        return
+    frac = min(1.0, DUMP_BYTES / 4.0 / sum(a.size for a in arrays.values()))
+    os.makedirs(directory, exist_ok=True)
+    for (s, c), a in arrays.items():
+        if frac < 1.0:
+            idx = np.random.default_rng(s * c).choice(a.size, int(a.size * frac), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(directory, f"out_s{s}_c{c}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -527,8 +561,13 @@ def main():
     if name == "auto":
         name = args.model or ("sdxl" if world == 1 else "seq16")
     wl = build_workload(name, args, world, rank, device, torch, aid_amd)
+    also_min_seconds = 1.0 if args.min_seconds is None else args.min_seconds
     tm = time_workload(wl, args, world, device, torch, dist)
     shard, loop, steps = wl["shard"], wl["loop"], args.steps
+    outputs = tm.pop("outputs")
+    if args.dump_outputs:
+        dump_outputs(outputs, shard, args.dump_outputs, rank)
+    del outputs
 
     result = {
         "metric": "interpolation-frames/sec (50-step)",
@@ -586,7 +625,7 @@ def main():
         # (replicated end points make the ideal speed-up n_total / max_local_batch, not the rank count)
         result["config"]["busiest_rank_local_frames_per_s"] = mlb / (tm["ms_per_step"] * 50.0 / 1000.0)
 
-    if not args.no_roofline and (rank == 0 or args.endpoints == "exchange"):
+    if args.full and not args.no_roofline and (rank == 0 or args.endpoints == "exchange"):
         # N > 1: rank 0's LOCAL batch.  Replicated end points: no collective inside a step, so rank 0 times its kernels alone;
         # the exchange layout broadcasts per layer, so every rank walks the profiled steps and rank 0 reports
         prof = roofline_pass(loop, aid_amd, torch)
@@ -594,10 +633,11 @@ def main():
             result["roofline"] = roofline_object(prof, wl["stack"], wl["dtype"])
             if world > 1:
                 result["roofline"]["scope"] = f"rank 0 of {world}: local batch of {shard.n_local} frames"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and name != "ip":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and name != "ip":
         result["cpu_baseline"] = cpu_baseline(wl["stack"], wl["n_total"], wl["early"], steps, args.warmup_ratio)
-    if rank == 0 and world == 1 and name == "sdxl" and args.workload == "auto" and not args.model and not args.no_also:
+    if args.full and rank == 0 and world == 1 and name == "sdxl" and args.workload == "auto" and not args.model and not args.no_also:
         # BASELINE's metric names SD1.5 512^2 AND SDXL 1024^2: the SD1.5 half rides along (same steps / repeats rule)
+        args.min_seconds = also_min_seconds
         del wl, loop
         torch.cuda.empty_cache()
         w2 = build_workload("sd15", args, world, rank, device, torch, aid_amd)

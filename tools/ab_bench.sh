@@ -3,7 +3,7 @@
 m=$1; shift
 for rep in 1 2; do
 for e in "$@"; do
-  env $e timeout 300 python bench.py --model $m --no-cpu-baseline 2>/dev/null | python -c "
+  env $e timeout 300 python bench.py --model $m --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

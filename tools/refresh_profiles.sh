@@ -3,18 +3,19 @@
 # collection (tools/pmc_collect.py), the per-launch breakdown of both stacks, the projection microbenchmark, the attention
 # A/B table of the knobs that decide the variants, the sublayer modes.
 set -x
+ROOT=$(pwd)
 R=gpurun_out/r06; mkdir -p $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $R/bench_default.json 2> $R/bench_default.err
-timeout 400 python bench.py --workload ip --steps 20 --warmup 5 > $R/bench_ip.json 2> $R/bench_ip.err
-timeout 400 python bench.py --workload seq16 --steps 20 --warmup 5 --no-cpu-baseline > $R/bench_seq16.json 2> $R/bench_seq16.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $R/bench_default.json 2> $R/bench_default.err
+timeout 400 python bench.py --full --workload ip --steps 20 --warmup 5 > $R/bench_ip.json 2> $R/bench_ip.err
+timeout 400 python bench.py --full --workload seq16 --steps 20 --warmup 5 --no-cpu-baseline > $R/bench_seq16.json 2> $R/bench_seq16.err
 cd /tmp && export TMPDIR=/tmp
 for w in sdxl sd15; do
   rm -rf /tmp/prof_$w
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$w -- python $GRAFT_REPO_ROOT/bench.py --workload $w --steps 8 --warmup 2 --no-cpu-baseline --no-also --min-seconds 0 $([ $w = sd15 ] && echo --passes serial) > $GRAFT_REPO_ROOT/$R/${w}_bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$R/${w}_rocprof.err
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$w -- python $ROOT/bench.py --full --workload $w --steps 8 --warmup 2 --no-cpu-baseline --no-also --min-seconds 0 $([ $w = sd15 ] && echo --passes serial) > $ROOT/$R/${w}_bench_under_rocprof.json 2> $ROOT/$R/${w}_rocprof.err
   db=$(ls -S $(find /tmp/prof_$w -name '*.db') | head -1)      # the bench's own database, not the one of the mfma_ceiling subprocess it starts
-  python $GRAFT_REPO_ROOT/tools/rocprof_summary.py $db $GRAFT_REPO_ROOT/$R/${w}_kernel_stats.txt > /dev/null
+  python $ROOT/tools/rocprof_summary.py $db $ROOT/$R/${w}_kernel_stats.txt > /dev/null
 done
-cd $GRAFT_REPO_ROOT
+cd $ROOT
 for w in sdxl sd15; do python tools/stack_breakdown.py $w > $R/breakdown_$w.txt 2>/dev/null; done
 python tools/kbench_proj.py > $R/kbench_proj.txt 2>/dev/null
 python tools/kbench_attn_ab.py "ATTN_V2=-1" "ATTN_V2=0" --rounds 5 --iters 6 --shapes sdxl --inner > $R/kbench_attn.txt 2>/dev/null
