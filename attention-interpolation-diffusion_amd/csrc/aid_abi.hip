@@ -76,17 +76,15 @@ struct ProfScope {          // records an event pair around one launch when prof
 const char* const g_tune_names[aid::TUNE_COUNT] = {"GEMM_VARIANT", "GEMM_PP", "GEMM_TRI", "ATTN_NW", "ATTN_QB", "ATTN_PIPE",
                                                    "ATTN_RES", "ATTN_RES_CHUNKS", "ATTN_ORDER", "ATTN_V2", "CU_SHARE", "GEMM_RS", "ATTN_TX", "ATTN_TX_TILES", "GEMM_LS"};
 // Largest value a knob accepts.  Every accepted value selects between kernels / launch shapes that compute THE SAME RESULT (the parity
-// suite runs under each of them); values beyond the range are refused by aid_set_tuning and ignored in the environment.  The timing
-// ablations (kernels that skip work, "results are garbage") exist only in development builds (-DAID_ABLATIONS, tools/dev/Makefile ->
-// tools/dev/libaid_abl.so) and are addressed through the same table there.
-#ifdef AID_ABLATIONS
-const int g_tune_max[aid::TUNE_COUNT] = {31, 15, 1, 8, 2, 1, 1, 1000, 1, 1, 8, 1, 1, 64, 1};
-#else
-#if defined(AID_RS_VARIANTS) || defined(AID_PPX_ORDERS)
+// suite runs under each of them); values beyond the range are refused by aid_set_tuning and ignored in the environment.  Development
+// builds (tools/dev/Makefile) widen two ranges: the attention timing ablations (kernels that skip work, "results are garbage";
+// -DAID_ABLATIONS) are ATTN_RES_CHUNKS > 100, the row-stationary GEMM's stamps / ablations (-DAID_RS_VARIANTS) GEMM_PP up to 7.
+#if defined(AID_ABLATIONS)
+const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 1000, 1, 1, 8, 1, 1, 64, 1};
+#elif defined(AID_RS_VARIANTS)
 const int g_tune_max[aid::TUNE_COUNT] = {31, 7, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1};
 #else
 const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1};
-#endif
 #endif
 struct TuneTable {
     std::atomic<int> v[aid::TUNE_COUNT];        // independent integers: a knob flipped by one thread is seen by the launches of all
@@ -349,14 +347,10 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
             g_gemm_variant = "f32";
             ps.rename("aid_gemm_f32_kernel");
         } else {
-            e = aid::gemm_group_launch(g, dtype, static_cast<hipStream_t>(stream), &g_gemm_variant, problems[0].cu_share);
             // profile entries carry the kernel SYMBOL that ran, so they line up with rocprofv3's per-kernel rows
+            const char* sym = "aid_gemm_nt_kernel";
+            e = aid::gemm_group_launch(g, dtype, static_cast<hipStream_t>(stream), &g_gemm_variant, &sym, problems[0].cu_share);
             char nm[64];
-            const char* sym = !strncmp(g_gemm_variant, "rowstat", 7)      ? "aid_gemm_rs_kernel"
-                              : !strncmp(g_gemm_variant, "pingpong288", 11) ? "aid_gemm_nt_ppx_kernel"
-                              : !strncmp(g_gemm_variant, "pingpong", 8)   ? "aid_gemm_nt_pp_kernel"
-                              : !strcmp(g_gemm_variant, "edge")           ? "aid_gemm_nt_kernel"
-                                                                          : "aid_gemm_nt_pipe_kernel";
             snprintf(nm, sizeof(nm), "%s<%s>", sym, dtype_name(dtype));
             ps.rename(nm);
         }

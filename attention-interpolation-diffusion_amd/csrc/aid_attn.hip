@@ -1082,7 +1082,7 @@ __global__ __launch_bounds__(NW * 64) void aid_attn_kernel(const AttnKParams p) 
                     T8 v = *reinterpret_cast<const T8*>(stg + row * RBY + ((SWZ ? cc ^ ((row >> 1) & 7) : cc) << 4));
                     const int q = q0 + row;
                     const int vo = (min(q, a.s - 1) * a.ldo + cc * 8) * 2;
-                    if (q < a.s) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, vo, so, AID_ST_AUX);
+                    if (q < a.s) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, vo, so, 0);
                 }
             }
         }
@@ -1127,15 +1127,10 @@ static hipError_t launch_variant(const AttnKParams& p, hipStream_t stream) {
     constexpr int NREG = MODE == AID_MODE_PLAIN ? 1 : MODE == AID_MODE_INNER ? 2 : 3;
     const size_t smem = RES ? ((size_t)NREG * (RES_KEYS * (DK + 8) + DV * RES_VLD) + RES_SLACK) * sizeof(T)
                             : (size_t)((attn_prefetch(D, NW) || QB > 1) ? 2 : 1) * (KT * (DK + 8) + DV * VLD) * sizeof(T);
-    static PerDevice<bool> attr_set;
-    bool* done = attr_set.slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&aid_attn_kernel<T, D, MODE, NW, QB, PIPE, RES, BIAS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        *done = true;
-    }
+    static PerDevice<int> attr_set;
+    const hipError_t e =
+        set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(&aid_attn_kernel<T, D, MODE, NW, QB, PIPE, RES, BIAS>), smem);
+    if (e != hipSuccess) return e;
     const int grid = p.nqb * p.a.n_frames * p.a.heads;
     hipLaunchKernelGGL((aid_attn_kernel<T, D, MODE, NW, QB, PIPE, RES, BIAS>), dim3(grid), dim3(NW * 64), smem, stream, p);
     return hipGetLastError();

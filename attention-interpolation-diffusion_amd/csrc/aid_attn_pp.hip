@@ -650,7 +650,7 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
                 const int q = q0 + row;
                 const int vo = (min(q, a.s - 1) * a.ldo + cc * 8) * 2;
                 if (a.accumulate) v = cvt8<T>(up8<T>(v) + up8<T>(__builtin_bit_cast(T8, __builtin_amdgcn_raw_buffer_load_b128(ro, vo, so, 0))));
-                if (q < a.s) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, vo, so, AID_ST_AUX);
+                if (q < a.s) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, vo, so, 0);
             }
         }
     };
@@ -787,10 +787,8 @@ hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) 
     p.abl = tune(TUNE_ATTN_RES_CHUNKS) > 100 ? tune(TUNE_ATTN_RES_CHUNKS) - 100 : 0;
 #endif
     const size_t smem = (size_t)PNS * PSTAGE + 8 * 4096;        // ring + the next item's Q rows
-    static PerDevice<int> attr_set[2];
+    static PerDevice<int> attr_set[2];                          // per dtype: one bit per mode
     const int ti = a.dtype == AID_DTYPE_F16 ? 0 : 1;
-    int* done = attr_set[ti].slot();
-    if (!done) return hipErrorInvalidDevice;
     if (a.mode < AID_MODE_PLAIN || a.mode > AID_MODE_OUTER) return hipErrorInvalidValue;
     const void* fns[2][3] = {
         {reinterpret_cast<const void*>(&aid_attn_pp_kernel<f16, AID_MODE_PLAIN>), reinterpret_cast<const void*>(&aid_attn_pp_kernel<f16, AID_MODE_INNER>),
@@ -799,11 +797,8 @@ hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) 
          reinterpret_cast<const void*>(&aid_attn_pp_kernel<bf16, AID_MODE_OUTER>)}};
     static_assert(AID_MODE_PLAIN == 0 && AID_MODE_INNER == 1 && AID_MODE_OUTER == 2, "mode index");
     const void* fn = fns[ti][a.mode];
-    if (!(*done & (1 << a.mode))) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        *done |= 1 << a.mode;
-    }
+    const hipError_t e = set_max_dynamic_lds(attr_set[ti], a.mode, fn, smem);
+    if (e != hipSuccess) return e;
     const int items = p.nqb * a.n_frames * a.heads;
     // persistent: the kernel owns every frame of the call (no early exits), every item is whole 8-tile trips, more items than CUs
     static PerDevice<int> cus;

@@ -375,12 +375,9 @@ static hipError_t tx_launch(const AttnTxParams& p, hipStream_t stream) {
     const size_t smem = (size_t)(outer ? 3 : 1) * TX_REGION;
     const void* fn = outer ? reinterpret_cast<const void*>(&aid_attn_tx_kernel<T, 3>) : reinterpret_cast<const void*>(&aid_attn_tx_kernel<T, 1>);
     static PerDevice<int> attr_set;
-    int* done = attr_set.slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (outer && !*done) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (outer) {                                              // (one region fits the default limit)
+        const hipError_t e = set_max_dynamic_lds(attr_set, 0, fn, smem);
         if (e != hipSuccess) return e;
-        *done = 1;
     }
     const int grid = p.a.heads * p.a.n_frames * p.chunks;
     void* kargs[] = {const_cast<AttnTxParams*>(&p)};

@@ -3,13 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Cache policy of the big output stores (buffer-store aux bits on gfx950: 1 = sc0, 2 = nt, 16 = sc1).  0 = plain write-back stores (the
-// product); development builds (tools/dev/Makefile, libaid_st<aux>.so) try the others: a kernel boundary is a release of everything
-// the kernel left dirty in the L2s, and write-through stores leave nothing dirty (profiles/r06_notes.md).
-#ifndef AID_ST_AUX
-#define AID_ST_AUX 0
-#endif
-
 namespace aid {
 
 typedef _Float16 f16;
@@ -131,5 +124,16 @@ struct PerDevice {
         return &v[d];
     }
 };
+
+// Raises `kernel`'s dynamic-LDS limit to `bytes` on the current device, once: bit `bit` of the device's entry of `done` (storage the
+// caller owns) records that it is set.  Returns the HIP error of the attempt, hipSuccess when it was set before.
+inline hipError_t set_max_dynamic_lds(PerDevice<int>& done, int bit, const void* kernel, size_t bytes) {
+    int* d = done.slot();
+    if (!d) return hipErrorInvalidDevice;
+    if (*d & (1 << bit)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) *d |= 1 << bit;
+    return e;
+}
 
 }  // namespace aid

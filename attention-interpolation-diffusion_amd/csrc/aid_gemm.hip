@@ -345,7 +345,7 @@ __device__ __forceinline__ void store_rows_fast(const T* Cs, T* C, const T* R, i
             T8 o = v[i];
             if (R) o = cvt8<T>(up8<T>(v[i]) + up8<T>(r[i]));
             if (r0 + RPP * (g0 + i) < rows_valid)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rc, voff, (g0 + i) * pass, AID_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rc, voff, (g0 + i) * pass, 0);
         }
     }
 }
@@ -828,44 +828,27 @@ struct PingPong : Engine<T, 256, 256, 64, 2, 2, 4> {
         dma_one<Q>(t & 1, (kb + t) * 64, 0);
         dma_one<Q>(t & 1, (kb + t) * 64, 1);
     }
-    // ABL (timing ablations, results are garbage): bit 0 = no DMAs in the loop, bit 1 = no fragment reads in the loop
-    template <bool PRIO, int ABL = 0>
+    template <bool PRIO>
     __device__ __forceinline__ void mac_rd(int kb, int ke) {
         const int nk = ke - kb;
-        constexpr bool NODMA = ABL & 1, NORD = ABL & 2;
         dma_half<0>(0, kb); dma_half<1>(0, kb); dma_half<2>(0, kb); dma_half<3>(0, kb);
         if (nk > 1) { dma_half<0>(1, kb); dma_half<1>(1, kb); wait_vmcnt<6>(); }
         else        wait_vmcnt<2>();
         slot();
         if (wr == 1) slot();                // the second group runs one barrier behind
         T8 fa[2][4], fb[2][4];
-        if (NORD) { read_b(fb, smem); read_a(fa, smem, 0); }
         auto body = [&](int kt, auto more1_t, auto more2_t) __attribute__((always_inline)) {
-            constexpr bool M1 = decltype(more1_t)::value && !NODMA, M2 = decltype(more2_t)::value && !NODMA;   // tile kt + 1 / kt + 2 exists
+            constexpr bool M1 = decltype(more1_t)::value, M2 = decltype(more2_t)::value;   // tile kt + 1 / kt + 2 exists
             const char* st = smem + (kt & 1) * STG;
-            if (!NORD) {
-                read_b(fb, st);
-                read_a(fa, st, 0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) { asm volatile("" : "+v"(fa[e][ks])); asm volatile("" : "+v"(fb[e][ks])); }
-            }
+            read_b(fb, st);
+            read_a(fa, st, 0);
             if (M1) { dma_half<2>(kt + 1, kb); dma_half<3>(kt + 1, kb); }
             if (M1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
             else    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             slot();
             half<0, false, PRIO>(fb, fa, kt, kb, nk);
             slot();
-            if (!NORD) {
-                read_a(fa, st, 1);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(fa[e][ks]));
-            }
+            read_a(fa, st, 1);
             if (M2) { dma_half<0>(kt + 2, kb); dma_half<1>(kt + 2, kb); }
             if (M2)      asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
             else if (M1) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
@@ -948,10 +931,6 @@ struct PingPongX : PingPong<T> {
     using PP::ra; using PP::rb; using PP::avo; using PP::bvo;
     f32x16 accx;
     int xoff, xx, xvo;
-    int kmul = 128;             // bytes per K tile in the DMA's scalar offset (development order 4 freezes it at 0: every request an L2 hit)
-#ifdef AID_ABLATIONS
-    int abl_ = 0;               // development builds: 4 = epilogue without the global stores, 8 = without the staging pass
-#endif
 
     __device__ __forceinline__ void init(char* smem_) {
         PP::init(smem_);
@@ -977,19 +956,12 @@ struct PingPongX : PingPong<T> {
         for (int j = 0; j < 2; ++j) {
             char* dst = smem + (t & 1) * STGX + (IS_A ? 0 : 2 * HALF) + H * HALF + wave * 2048 + j * 1024;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(IS_A ? ra : rb, (__attribute__((address_space(3))) void*)dst, 16,
-                                                     IS_A ? avo[H * 2 + j] : bvo[H * 2 + j], (kb + t) * kmul, 0, 0);
+                                                     IS_A ? avo[H * 2 + j] : bvo[H * 2 + j], (kb + t) * 128, 0, 0);
         }
-    }
-    __device__ __forceinline__ void xdma_one(const int Q, const int j, int t, int kb) {     // piece j (0 / 1) of half-tile Q
-        const bool IS_A = Q >= 2;
-        const int H = Q & 1;
-        char* dst = smem + (t & 1) * STGX + (IS_A ? 0 : 2 * HALF) + H * HALF + wave * 2048 + j * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(IS_A ? ra : rb, (__attribute__((address_space(3))) void*)dst, 16,
-                                                 IS_A ? avo[H * 2 + j] : bvo[H * 2 + j], (kb + t) * kmul, 0, 0);
     }
     __device__ __forceinline__ void dma_strip(int t, int kb) {  // waves 0 - 3 only
         char* dst = smem + (t & 1) * STGX + 4 * HALF + wave * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, xvo, (kb + t) * kmul, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, xvo, (kb + t) * 128, 0, 0);
     }
     __device__ __forceinline__ void read_x(T8 (&fx)[4], const char* st) {
 #pragma unroll
@@ -1008,14 +980,10 @@ struct PingPongX : PingPong<T> {
     // TR: the problem wants C transposed per frame (GemmDesc.trans_rows): the MFMAs are issued the other way round
     // (D rows = m, columns = n), so a lane ends up with four consecutive ROWS of one output column and the staged tile
     // can be written n-major with the same 8-byte stores.
-    // ORD (development build -DAID_PPX_ORDERS, GEMM_PP = 4 .. 6; same arithmetic, same results): where a read slot issues its LDS-DMA
-    // requests — 0 behind the fragment reads (round 3, the product), 1 in front of them, 2 one request per four reads; 3 = order 0 with
-    // s_setprio 1 on the MFMA slots
-    template <int WR, bool TR, int ORD>
+    template <int WR, bool TR>
     __device__ __forceinline__ void mac_x(int kb, int ke) {
         const int nk = ke - kb;
         const bool xw = wave < 4;
-        if (ORD == 4) kmul = 0;             // (timing only, results are garbage: the K loop with every operand request served by the L2)
         xdma_half(0, 0, kb); xdma_half(1, 0, kb); xdma_half(2, 0, kb); xdma_half(3, 0, kb);
         if (xw) dma_strip(0, kb);
         if (nk > 1) {
@@ -1030,49 +998,25 @@ struct PingPongX : PingPong<T> {
         auto body = [&](int kt, auto more1_t, auto more2_t) __attribute__((always_inline)) {
             constexpr bool M1 = decltype(more1_t)::value, M2 = decltype(more2_t)::value;   // tile kt + 1 / kt + 2 exists
             const char* st = smem + (kt & 1) * STGX;
-            auto rdb = [&](int j) __attribute__((always_inline)) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fb[j][ks] = *reinterpret_cast<const T8*>(st + boff[0] + j * HALF + (((2 * ks) ^ bx[0]) << 4));
-            };
-            auto rda = [&](int e, int h) __attribute__((always_inline)) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[e][ks] = *reinterpret_cast<const T8*>(st + h * HALF + aoff[e] + (((2 * ks) ^ ax[e]) << 4));
-            };
-            auto pinb = []() __attribute__((always_inline)) { __builtin_amdgcn_sched_barrier(0); };
-            if (ORD == 1 && M1) { xdma_half(2, kt + 1, kb); xdma_half(3, kt + 1, kb); if (xw) dma_strip(kt + 1, kb); pinb(); }
-            if (ORD == 2 && M1) {
-                xdma_one(2, 0, kt + 1, kb); pinb(); rdb(0); pinb(); xdma_one(2, 1, kt + 1, kb); pinb(); rdb(1); pinb();
-                xdma_one(3, 0, kt + 1, kb); pinb(); rda(0, 0); pinb(); xdma_one(3, 1, kt + 1, kb); pinb(); rda(1, 0); pinb();
-                if (xw) dma_strip(kt + 1, kb);
-            } else {
-                this->read_b(fb, st);
-                this->read_a(fa, st, 0);
-            }
+            this->read_b(fb, st);
+            this->read_a(fa, st, 0);
             if (M1) {
-                if (ORD == 0 || ORD >= 3) { xdma_half(2, kt + 1, kb); xdma_half(3, kt + 1, kb); if (xw) dma_strip(kt + 1, kb); }
+                xdma_half(2, kt + 1, kb); xdma_half(3, kt + 1, kb); if (xw) dma_strip(kt + 1, kb);
                 wait_rd<8>(xw);
             } else {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             }
             PP::slot();
-            if (ORD == 3) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int ks = i >> 2, in = (i >> 1) & 1, e = i & 1;
                 acc[in][e] = TR ? mfma32(fa[e][ks], fb[in][ks], acc[in][e]) : mfma32(fb[in][ks], fa[e][ks], acc[in][e]);
             }
-            if (ORD == 3) __builtin_amdgcn_s_setprio(0);
             PP::slot();
-            if (ORD == 1 && M2) { xdma_half(0, kt + 2, kb); xdma_half(1, kt + 2, kb); pinb(); }
-            if (ORD == 2 && M2) {
-                xdma_one(0, 0, kt + 2, kb); pinb(); rda(0, 1); pinb(); xdma_one(0, 1, kt + 2, kb); pinb(); rda(1, 1); pinb();
-                xdma_one(1, 0, kt + 2, kb); pinb(); read_x(fx, st); pinb(); xdma_one(1, 1, kt + 2, kb);
-            } else {
-                this->read_a(fa, st, 1);
-                read_x(fx, st);
-            }
+            this->read_a(fa, st, 1);
+            read_x(fx, st);
             if (M2) {
-                if (ORD == 0 || ORD >= 3) { xdma_half(0, kt + 2, kb); xdma_half(1, kt + 2, kb); }
+                xdma_half(0, kt + 2, kb); xdma_half(1, kt + 2, kb);
                 wait_rd<6>(xw);
             } else if (M1) {
                 wait_rd<2>(xw);
@@ -1080,7 +1024,6 @@ struct PingPongX : PingPong<T> {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             }
             PP::slot();
-            if (ORD == 3) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int ks = i >> 2, in = (i >> 1) & 1, e = i & 1;
@@ -1088,7 +1031,6 @@ struct PingPongX : PingPong<T> {
                 if ((i & 3) == 3)                                               // the strip's block: this wave's own B fragment
                     accx = TR ? mfma32(fx[ks], fb[WR][ks], accx) : mfma32(fb[WR][ks], fx[ks], accx);
             }
-            if (ORD == 3) __builtin_amdgcn_s_setprio(0);
             PP::slot();
         };
         const std::true_type Y{};
@@ -1104,36 +1046,16 @@ struct PingPongX : PingPong<T> {
     // Whole tile: four copies of (K loop + epilogue) — fb[WR] must be a compile-time register choice and the operand order
     // a compile-time choice; the epilogue sits INSIDE each copy so that no accumulator crosses a control-flow merge (with a
     // common epilogue behind the four loops hipcc spilled 80 accumulator registers at the join).
-    template <int ORD>
-    __device__ __forceinline__ void run_tile(const GemmDesc& P, T* C, int batch, int m0, int n0
-#ifdef AID_ABLATIONS
-                                             , int abl = 0
-#endif
-                                             ) {
+    __device__ __forceinline__ void run_tile(const GemmDesc& P, T* C, int batch, int m0, int n0) {
         const int nk = P.k / 64;
         const T* R = P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)batch * P.stride_c : nullptr;
         const float* st = P.ln_stats ? P.ln_stats + 2 * (int64_t)batch * P.stride_stats : nullptr;
         if (P.trans_rows) {
-            if (wr == 0) { mac_x<0, true, ORD>(0, nk); store_tile_t(P, reinterpret_cast<T*>(P.c), m0, n0, P.ln_stats); }
-            else         { mac_x<1, true, ORD>(0, nk); store_tile_t(P, reinterpret_cast<T*>(P.c), m0, n0, P.ln_stats); }
+            if (wr == 0) { mac_x<0, true>(0, nk); store_tile_t(P, reinterpret_cast<T*>(P.c), m0, n0, P.ln_stats); }
+            else         { mac_x<1, true>(0, nk); store_tile_t(P, reinterpret_cast<T*>(P.c), m0, n0, P.ln_stats); }
         } else {
-#ifdef AID_ABLATIONS
-            // (timing ablations of development builds — 1 = no epilogue, 2 = no K loop; one call site per instantiation: a second
-            //  `mac_x<1, false>` call elsewhere fails to instantiate in hipcc's host pass)
-            abl_ = abl;
-            if (wr == 0) { if (!(abl & 2)) mac_x<0, false, ORD>(0, nk); if (!(abl & 1)) store_tile(P, C, m0, n0, R, st); }
-            else         { if (!(abl & 2)) mac_x<1, false, ORD>(0, nk); if (!(abl & 1)) store_tile(P, C, m0, n0, R, st); }
-            if (abl & 1) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-                asm volatile("" ::"v"(accx));
-            }
-#else
-            if (wr == 0) { mac_x<0, false, ORD>(0, nk); store_tile(P, C, m0, n0, R, st); }
-            else         { mac_x<1, false, ORD>(0, nk); store_tile(P, C, m0, n0, R, st); }
-#endif
+            if (wr == 0) { mac_x<0, false>(0, nk); store_tile(P, C, m0, n0, R, st); }
+            else         { mac_x<1, false>(0, nk); store_tile(P, C, m0, n0, R, st); }
         }
     }
 
@@ -1262,11 +1184,7 @@ struct PingPongX : PingPong<T> {
         const int side = stats ? P.ln_side : 0;
         float* const lnr = reinterpret_cast<float*>(smem + (size_t)BMX * CLD * 2);    // [BMX][2]
         float* const lnc = lnr + 2 * BMX;                                             // [BN][2]
-        if (epilogue_fast_ok<T>(P, C, R, n0, BN)
-#ifdef AID_ABLATIONS
-            && !(abl_ & 12)
-#endif
-        ) {                                                     // straight-line epilogue (see stage_block_fast)
+        if (epilogue_fast_ok<T>(P, C, R, n0, BN)) {             // straight-line epilogue (see stage_block_fast)
             if (side) {
                 for (int i = tid; i < BMX + BN; i += NTHR) {
                     const bool isrow = i < BMX;
@@ -1333,26 +1251,11 @@ struct PingPongX : PingPong<T> {
                 *reinterpret_cast<T4*>(Cs + row * CLD + nl) = cvt4<T>(v);
             }
         };
-#ifdef AID_ABLATIONS
-        if (!(abl_ & 8))
-#endif
-        {
 #pragma unroll
         for (int in = 0; in < 2; ++in)
 #pragma unroll
             for (int im = 0; im < 4; ++im) stage(acc[in][im], wm + im * 32, wn + in * 32);
         stage(accx, 256, wn + wr * 32);
-        }
-#ifdef AID_ABLATIONS
-        if (abl_ & 8) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) asm volatile("" ::"v"(acc[i][jj]));
-            asm volatile("" ::"v"(accx));
-        }
-        if (abl_ & 4) return;
-#endif
         __syncthreads();
         const bool vec_ok = (P.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
         constexpr int CPRW = BN / 8;               // 16-B chunks per C row
@@ -1390,26 +1293,35 @@ struct PingPongX : PingPong<T> {
 static_assert((288 * 32) % 512 == 0 && (256 * 36) % 512 == 0, "C rows divide over the threads");
 static_assert(Engine<bf16, 128, 128, 64, 4, 2, 4>::SMEM <= PingPongX<bf16>::SMEMX, "side tiles use the big tile's LDS");
 
-template <typename T, int ORD = 0>
-__global__ __launch_bounds__(512) void aid_gemm_nt_ppx_kernel(const GemmGroup g, const GemmSide sd
-#ifdef AID_ABLATIONS
-                                                              , const int abl      // development builds only: timing ablations
-#endif
-                                                              ) {
+// Side tile u (< sd.tiles) of a ping-pong launch: the 128 x 128 tiles of the side problems, one problem after the other.
+// (The lock-step tile body itself stays written out at each site below: moved into a shared inline helper, which the compiler
+//  optimises on its own before inlining it, it changed the machine code of the pipe and ping-pong kernels.)
+__device__ __forceinline__ TileCoord locate_side(const GemmSide& sd, int u) {
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (i < sd.n && u >= sd.tile_start[i]) pi = i;
+    const GemmDesc& P = sd.p[pi];
+    int rem = u - sd.tile_start[pi];
+    const int tiles_n = (P.n + 127) / 128, per_batch = ((P.m + 127) / 128) * tiles_n;
+    TileCoord t;
+    t.p = pi;
+    t.batch = rem / per_batch;
+    rem -= t.batch * per_batch;
+    t.m0 = (rem / tiles_n) * 128;
+    t.n0 = (rem % tiles_n) * 128;
+    return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void aid_gemm_nt_ppx_kernel(const GemmGroup g, const GemmSide sd) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     if ((int)blockIdx.x < sd.pad_tiles) {                          // side problems first (see aid_gemm_nt_pp_kernel)
         const int u = blockIdx.x;
         if (u >= sd.tiles) return;
-        int pi = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < sd.n && u >= sd.tile_start[i]) pi = i;
-        const GemmDesc& P = sd.p[pi];
-        int rem = u - sd.tile_start[pi];
-        const int tiles_n = (P.n + 127) / 128, per_batch = ((P.m + 127) / 128) * tiles_n;
-        const int batch = rem / per_batch;
-        rem -= batch * per_batch;
-        const int m0 = (rem / tiles_n) * 128, n0 = (rem % tiles_n) * 128;
+        const TileCoord t = locate_side(sd, u);
+        const GemmDesc& P = sd.p[t.p];
+        const int batch = t.batch, m0 = t.m0, n0 = t.n0;
         const T* A = reinterpret_cast<const T*>(P.a) + (int64_t)batch * P.stride_a;
         const T* B = reinterpret_cast<const T*>(P.b) + (int64_t)batch * P.stride_b;
         T* C = reinterpret_cast<T*>(P.c) + (int64_t)batch * P.stride_c;
@@ -1432,11 +1344,7 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_ppx_kernel(const GemmGroup g,
     e.init(smem_raw);
     e.set_tile(P, A, B, tc.m0, tc.n0);
     e.zero_acc();
-#ifdef AID_ABLATIONS
-    e.template run_tile<ORD>(P, C, tc.batch, tc.m0, tc.n0, abl);
-#else
-    e.template run_tile<ORD>(P, C, tc.batch, tc.m0, tc.n0);
-#endif
+    e.run_tile(P, C, tc.batch, tc.m0, tc.n0);
 }
 
 template <typename T, int PPV>
@@ -1445,16 +1353,9 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
     if ((int)blockIdx.x < sd.pad_tiles) {                          // side problems first: their long K loops start at once
         const int u = blockIdx.x;
         if (u >= sd.tiles) return;
-        int pi = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < sd.n && u >= sd.tile_start[i]) pi = i;
-        const GemmDesc& P = sd.p[pi];
-        int rem = u - sd.tile_start[pi];
-        const int tiles_n = (P.n + 127) / 128, per_batch = ((P.m + 127) / 128) * tiles_n;
-        const int batch = rem / per_batch;
-        rem -= batch * per_batch;
-        const int m0 = (rem / tiles_n) * 128, n0 = (rem % tiles_n) * 128;
+        const TileCoord t = locate_side(sd, u);
+        const GemmDesc& P = sd.p[t.p];
+        const int batch = t.batch, m0 = t.m0, n0 = t.n0;
         const T* A = reinterpret_cast<const T*>(P.a) + (int64_t)batch * P.stride_a;
         const T* B = reinterpret_cast<const T*>(P.b) + (int64_t)batch * P.stride_b;
         T* C = reinterpret_cast<T*>(P.c) + (int64_t)batch * P.stride_c;
@@ -1480,7 +1381,6 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
         e.zero_acc();
         if (PPV == 1)      e.template mac_rd<false>(0, P.k / 64);
         else if (PPV == 2) e.template mac_rd<true>(0, P.k / 64);
-        else if (PPV >= 4) e.template mac_rd<false, PPV - 4>(0, P.k / 64);
         else               e.mac(0, P.k / 64);
         e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
                      P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
@@ -1525,7 +1425,16 @@ __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const Ge
 }
 
 // ------------------------------------------------------------------------------------------------
-static int plan_tiles(GemmGroup& g, int bm, int bn) {
+// Host side: plan_gemm picks the engine of a group and launches nothing; launch_plan runs the plan.
+// ------------------------------------------------------------------------------------------------
+static int count_tiles(const GemmGroup& g, int bm, int bn) {
+    int tiles = 0;
+    for (int i = 0; i < g.n_problems; ++i) tiles += ((g.p[i].m + bm - 1) / bm) * ((g.p[i].n + bn - 1) / bn) * g.p[i].batch;
+    return tiles;
+}
+
+// g.tile_start (the kernels' block -> problem map) in units of bm x bn tiles; returns the tile count
+static int fill_tile_start(GemmGroup& g, int bm, int bn) {
     int tiles = 0;
     for (int i = 0; i < g.n_problems; ++i) {
         g.tile_start[i] = tiles;
@@ -1536,26 +1445,57 @@ static int plan_tiles(GemmGroup& g, int bm, int bn) {
 }
 
 template <typename K>
-static hipError_t launch_with_smem(K kernel, size_t smem, PerDevice<bool>* attr_set, const GemmGroup& g, int total_tiles,
-                                   hipStream_t stream, int threads) {
-    if (total_tiles <= 0) return hipSuccess;
-    bool* done = attr_set->slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        *done = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3(total_tiles), dim3(threads), smem, stream, g);
+static hipError_t launch_with_smem(K kernel, size_t smem, PerDevice<int>& attr_set, GemmGroup& g, int bm, int bn, hipStream_t stream,
+                                   int threads) {
+    const int tiles = fill_tile_start(g, bm, bn);
+    if (tiles <= 0) return hipSuccess;
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(kernel), smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(threads), smem, stream, g);
     return hipGetLastError();
 }
 
-template <typename T, int BM, int BN, int BK, int NS, int WM, int WN>
+template <typename T>
+static hipError_t launch_edge(GemmGroup& g, hipStream_t stream) {
+    static PerDevice<int> attr_set;
+    return launch_with_smem(aid_gemm_nt_kernel<T>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), attr_set, g, GBM, GBN, stream, GTHREADS);
+}
+
+template <typename T, int NS>
 static hipError_t launch_pipe(GemmGroup& g, hipStream_t stream) {
-    static PerDevice<bool> attr_set;
-    return launch_with_smem(aid_gemm_nt_pipe_kernel<T, BM, BN, BK, NS, WM, WN>, Engine<T, BM, BN, BK, NS, WM, WN>::SMEM,
-                            &attr_set, g, plan_tiles(g, BM, BN), stream, WM * WN * 64);
+    static PerDevice<int> attr_set;
+    return launch_with_smem(aid_gemm_nt_pipe_kernel<T, 128, 128, 64, NS, 2, 4>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g,
+                            128, 128, stream, 512);
+}
+
+template <typename T, int PPV>
+static hipError_t launch_pp_v(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd) {
+    static PerDevice<int> attr_set;
+    if (fill_tile_start(g, 256, 256) <= 0) return hipSuccess;
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(aid_gemm_nt_pp_kernel<T, PPV>), PingPong<T>::SMEM);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((aid_gemm_nt_pp_kernel<T, PPV>), dim3(sd.pad_tiles + n_big + n_small), dim3(512), PingPong<T>::SMEM, stream,
+                       g, n_big, sd);
+    return hipGetLastError();
+}
+template <typename T>
+static hipError_t launch_pp(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd) {
+    switch (tune(TUNE_GEMM_PP)) {                   // K loop order (TUNE_GEMM_PP); unset and 3: 1
+        case 0:  return launch_pp_v<T, 0>(g, stream, n_big, n_small, sd);
+        case 2:  return launch_pp_v<T, 2>(g, stream, n_big, n_small, sd);
+        default: return launch_pp_v<T, 1>(g, stream, n_big, n_small, sd);
+    }
+}
+
+template <typename T>
+static hipError_t launch_ppx(GemmGroup& g, hipStream_t stream, const GemmSide& sd) {
+    static PerDevice<int> attr_set;
+    const int tiles = fill_tile_start(g, 288, 256);
+    if (tiles <= 0) return hipSuccess;
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(aid_gemm_nt_ppx_kernel<T>), PingPongX<T>::SMEMX);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(aid_gemm_nt_ppx_kernel<T>, dim3(sd.pad_tiles + tiles), dim3(512), PingPongX<T>::SMEMX, stream, g, sd);
+    return hipGetLastError();
 }
 
 static PerDevice<int> g_num_cu;
@@ -1572,105 +1512,84 @@ static int num_cu() {                       // CU count of the CURRENT device (c
     return *n;
 }
 
-// Plan of the ping-pong path: n_big 256 x 256 tiles (whole CU rounds) + the ragged rest as 128 x 128 tiles.
-struct PpPlan {
-    int tiles, n_big, n_small;
+// A ping-pong launch of `tiles` 256 x 256 tiles on ncu CUs: n_big of them (whole CU rounds) + the ragged rest as n_small 128 x 128 tiles.
+struct PpSplit {
+    int n_big, n_small;
     double rounds;                          // cost in units of one big-tile round
 };
-static PpPlan plan_pp(GemmGroup& g, int ncu, int nk) {
-    PpPlan pl;
-    pl.tiles = plan_tiles(g, 256, 256);
-    int full = pl.tiles / ncu, rest = pl.tiles % ncu;
-    pl.n_big = pl.tiles;
-    pl.n_small = 0;
-    pl.rounds = full + (rest ? 1 : 0);
+static PpSplit split_pp(int tiles, int ncu, int nk) {
+    PpSplit s;
+    const int full = tiles / ncu, rest = tiles % ncu;
+    s.n_big = tiles;
+    s.n_small = 0;
+    s.rounds = full + (rest ? 1 : 0);
     if (full > 0 && rest > 0 && rest <= ncu / 2 && ncu % 8 == 0) {   // a last round at <= 50 % occupancy: cut it up
-        pl.n_big = full * ncu;
-        pl.n_small = 4 * rest;
-        pl.rounds = full + ((4 * rest + ncu - 1) / ncu) * (2.0 + 0.6 * nk) / (6.0 + 1.62 * nk);
+        s.n_big = full * ncu;
+        s.n_small = 4 * rest;
+        s.rounds = full + ((4 * rest + ncu - 1) / ncu) * (2.0 + 0.6 * nk) / (6.0 + 1.62 * nk);
     }
-    return pl;
-}
-
-template <typename T, int PPV>
-static hipError_t launch_pp_v(GemmGroup& g, hipStream_t stream, const PpPlan& pl, const GemmSide& sd) {
-    static PerDevice<bool> attr_set;
-    if (pl.tiles <= 0) return hipSuccess;
-    if (plan_tiles(g, 256, 256) != pl.tiles) return hipErrorInvalidValue;      // g.tile_start must be in 256 x 256 units
-    bool* done = attr_set.slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(aid_gemm_nt_pp_kernel<T, PPV>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PingPong<T>::SMEM);
-        if (e != hipSuccess) return e;
-        *done = true;
-    }
-    hipLaunchKernelGGL((aid_gemm_nt_pp_kernel<T, PPV>), dim3(sd.pad_tiles + pl.n_big + pl.n_small), dim3(512), PingPong<T>::SMEM,
-                       stream, g, pl.n_big, sd);
-    return hipGetLastError();
-}
-template <typename T>
-static hipError_t launch_pp(GemmGroup& g, hipStream_t stream, const PpPlan& pl, const GemmSide& sd) {
-    switch (tune(TUNE_GEMM_PP)) {
-        case 1:  return launch_pp_v<T, 1>(g, stream, pl, sd);
-        case 0:  return launch_pp_v<T, 0>(g, stream, pl, sd);
-        case 2:  return launch_pp_v<T, 2>(g, stream, pl, sd);
-#ifdef AID_ABLATIONS
-        case 5:  return launch_pp_v<T, 5>(g, stream, pl, sd);      // no DMAs
-        case 6:  return launch_pp_v<T, 6>(g, stream, pl, sd);      // no fragment reads
-        case 7:  return launch_pp_v<T, 7>(g, stream, pl, sd);      // neither: MFMAs + barriers
-#endif
-        default: return launch_pp_v<T, 1>(g, stream, pl, sd);
-    }
-}
-
-
-template <typename T>
-static hipError_t launch_ppx(GemmGroup& g, hipStream_t stream, const GemmSide& sd) {
-    static PerDevice<bool> attr_set;
-    const int tiles = plan_tiles(g, 288, 256);
-    if (tiles <= 0) return hipSuccess;
-    bool* done = attr_set.slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(aid_gemm_nt_ppx_kernel<T>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PingPongX<T>::SMEMX);
-        if (e != hipSuccess) return e;
-        *done = true;
-    }
-#ifdef AID_ABLATIONS
-    const int abl = tune(TUNE_GEMM_PP) >= 8 ? tune(TUNE_GEMM_PP) - 8 : 0;
-    hipLaunchKernelGGL(aid_gemm_nt_ppx_kernel<T>, dim3(sd.pad_tiles + tiles), dim3(512), PingPongX<T>::SMEMX, stream, g, sd, abl);
-#else
-#ifdef AID_PPX_ORDERS
-    // development build (tools/dev/Makefile, libaid_ppxord.so): the read-slot orders of mac_x side by side, GEMM_PP = 4 / 5 / 6
-    const int ord = tune(TUNE_GEMM_PP) - 3;
-    auto go = [&](auto kern) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PingPongX<T>::SMEMX);
-        hipLaunchKernelGGL(kern, dim3(sd.pad_tiles + tiles), dim3(512), PingPongX<T>::SMEMX, stream, g, sd);
-    };
-    if (ord == 1)      go(aid_gemm_nt_ppx_kernel<T, 1>);
-    else if (ord == 2) go(aid_gemm_nt_ppx_kernel<T, 2>);
-    else if (ord == 3) go(aid_gemm_nt_ppx_kernel<T, 3>);
-    else if (ord == 4) go(aid_gemm_nt_ppx_kernel<T, 4>);      // timing ablation: garbage results
-    else               go(aid_gemm_nt_ppx_kernel<T, 0>);
-#else
-    hipLaunchKernelGGL(aid_gemm_nt_ppx_kernel<T>, dim3(sd.pad_tiles + tiles), dim3(512), PingPongX<T>::SMEMX, stream, g, sd);
-#endif
-#endif
-    return hipGetLastError();
+    return s;
 }
 
 // 288-row tiles pay when they turn a ragged last round into whole rounds: cost in rounds of a 256 x 256 tile, a 288-row
 // tile counted 9 / 8.  GEMM_TRI: 0 = never, 1 = whenever the shape allows (development knob; the name is historical).
-static bool prefer_ppx(GemmGroup& g, int ncu, const PpPlan& pl256) {
+static bool prefer_ppx(const GemmGroup& g, int ncu, double rounds256) {
     const int knob = tune(TUNE_GEMM_TRI);
     if (knob == 0) return false;
-    GemmGroup t = g;
-    const int tiles = plan_tiles(t, 288, 256);
-    const double r288 = 1.125 * (double)((tiles + ncu - 1) / ncu);
     if (knob == 1) return true;
-    return r288 < 0.97 * pl256.rounds;
+    const double r288 = 1.125 * (double)((count_tiles(g, 288, 256) + ncu - 1) / ncu);
+    return r288 < 0.97 * rounds256;
+}
+
+enum class GemmEngine { Edge, Lockstep, Lockstep4, Pp256, Pp256Tail, Pp288, Rowstat };
+
+// What runs a group, decided before anything is launched.
+struct GemmPlan {
+    GemmEngine engine;
+    GemmGroup g;                            // the problems it runs (ping-pong with side problems: the main ones); tile_start is
+                                            // filled by the launch, in the units of the engine that runs
+    GemmSide sd;                            // side problems of a ping-pong launch (sd.n = 0: none)
+    int n_big, n_small;                     // Pp256 / Pp256Tail: see split_pp
+    int ncu;                                // CUs the launch may count on (Rowstat: the split of its slice range)
+    const char* variant;                    // aid_last_gemm_variant()
+    const char* symbol;                     // kernel symbol, for the profile entries
+    bool writes_trans;                      // the engine writes the C of a trans_rows problem itself
+};
+
+static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide& sd, int ncu, int n_big = 0, int n_small = 0) {
+    GemmPlan pl;
+    pl.engine = engine;
+    pl.g = g;
+    pl.sd = sd;
+    pl.n_big = n_big;
+    pl.n_small = n_small;
+    pl.ncu = ncu;
+    const bool side = sd.n > 0;
+    switch (engine) {
+        case GemmEngine::Edge:      pl.variant = "edge";          pl.symbol = "aid_gemm_nt_kernel"; break;
+        case GemmEngine::Lockstep:  pl.variant = "lockstep128";   pl.symbol = "aid_gemm_nt_pipe_kernel"; break;
+        case GemmEngine::Lockstep4: pl.variant = "lockstep128x4"; pl.symbol = "aid_gemm_nt_pipe_kernel"; break;
+        case GemmEngine::Pp256:
+            pl.variant = side ? "pingpong256+side128" : "pingpong256";
+            pl.symbol = "aid_gemm_nt_pp_kernel";
+            break;
+        case GemmEngine::Pp256Tail:
+            pl.variant = side ? "pingpong256+tail128+side128" : "pingpong256+tail128";
+            pl.symbol = "aid_gemm_nt_pp_kernel";
+            break;
+        case GemmEngine::Pp288:
+            pl.variant = side ? "pingpong288+side128" : "pingpong288";
+            pl.symbol = "aid_gemm_nt_ppx_kernel";
+            break;
+        case GemmEngine::Rowstat:
+            pl.variant = g.p[0].k == 640 ? "rowstat640" : "rowstat320";
+            pl.symbol = "aid_gemm_rs_kernel";
+            break;
+    }
+    // transposed C: the row-stationary engine and the 288-row tiles write it; side tiles run on the 128 x 128 engine, which does not
+    pl.writes_trans = engine == GemmEngine::Rowstat || engine == GemmEngine::Pp288;
+    for (int i = 0; i < sd.n; ++i) pl.writes_trans = pl.writes_trans && !sd.p[i].trans_rows;
+    return pl;
 }
 
 // Two engines serve the k % 64 == 0 shapes; which one a launch gets is decided by a two-line cost model fitted to
@@ -1681,83 +1600,27 @@ static bool prefer_ppx(GemmGroup& g, int ncu, const PpPlan& pl256) {
 // The big tiles win on long K loops and many tiles (SDXL C = 1280: 170 -> 145 us, 69 -> 58 us); the small ones on
 // short K loops (SD1.5 C = 320), on launches of less than half a round, and whenever the K loops of a group differ
 // (the text-context projections of cross-attention: their tiles are mostly padding at 256 x 256).
-// A problem with trans_rows (C transposed per frame, the flat value projection E Wv^T -> V^T) runs as such only on the
-// 288-row engine.  Everywhere else it is rewritten into the equivalent batched product with swapped operands,
-// V^T[f] = Wv E_f^T  (m' = n channels, n' = trans_rows keys, one batch entry per frame) — what the callers issued before.
-static bool has_trans(const GemmGroup& g) {
-    for (int i = 0; i < g.n_problems; ++i)
-        if (g.p[i].trans_rows) return true;
-    return false;
-}
-static void untranspose(GemmGroup& g) {
-    for (int i = 0; i < g.n_problems; ++i) {
-        GemmDesc& d = g.p[i];
-        if (!d.trans_rows) continue;
-        const int rows = d.trans_rows, frames = d.m / rows;
-        GemmDesc o = d;
-        o.a = d.b; o.b = d.a;
-        o.m = d.n; o.n = rows;
-        o.lda = d.ldb; o.ldb = d.lda;
-        o.batch = frames;
-        o.stride_a = 0; o.stride_b = (int64_t)rows * d.lda;      // stride_c = frame stride of V^T already
-        if (d.ln_stats) { o.ln_side = 2; o.stride_stats = rows; }
-        o.trans_rows = 0;
-        d = o;
-    }
-}
-
-template <typename T>
-static hipError_t launch_gemm_sel(GemmGroup& g, hipStream_t stream, const char** variant, bool dry, bool* is_ppx, int cu_share);
-
-template <typename T>
-static hipError_t launch_gemm(GemmGroup& g, hipStream_t stream, const char** variant, int cu_share) {
-    if (has_trans(g)) {
-        GemmGroup probe = g;
-        bool ppx = false;
-        const hipError_t e = launch_gemm_sel<T>(probe, stream, nullptr, true, &ppx, cu_share);
-        if (e != hipSuccess) return e;
-        if (!ppx) untranspose(g);
-    }
-    return launch_gemm_sel<T>(g, stream, variant, false, nullptr, cu_share);
-}
-
-// dry: pick the engine only (*is_ppx = the 288-row engine would run the main problems), launch nothing
-template <typename T>
-static hipError_t launch_gemm_sel(GemmGroup& g, hipStream_t stream, const char** variant, bool dry, bool* is_ppx, int cu_share) {
+// Two CU counts: `device_cu` is the device's, `ncu` (device_cu after the CU_SHARE hint) the one the tile engines plan with.  The
+// row-stationary size rule and the GEMM_LS default look at the device's.
+static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share) {
+    GemmSide sd;
+    memset(&sd, 0, sizeof(sd));
     bool k64 = true;
     for (int i = 0; i < g.n_problems; ++i) k64 = k64 && (g.p[i].k % 64 == 0);
-    if (!k64) {
-        static PerDevice<bool> s0;
-        if (dry) return hipSuccess;
-        if (variant) *variant = "edge";
-        return launch_with_smem(aid_gemm_nt_kernel<T>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), &s0, g,
-                                plan_tiles(g, GBM, GBN), stream, GTHREADS);
-    }
+    if (!k64) return make_plan(GemmEngine::Edge, g, sd, device_cu);
     // development knob (tools/gemm_shapes.py): AID_GEMM_VARIANT=7 / 31 forces the lock-step / ping-pong engine
     const int force = tune(TUNE_GEMM_VARIANT);
-    int ncu = num_cu();
-    if (ncu <= 0) return hipErrorInvalidDevice;
     // CU_SHARE = n: n launch streams share the device (the two passes of a step on two streams): a launch can count on 1 / n of the
     // CUs, so e.g. 125 tiles of 288 rows are a full round, not half of one (SDXL, two streams: 39.0 -> 37.3 ms/step)
     // (the per-call value — AidGemmProblem.cu_share — wins over the process-wide knob)
     const int share = cu_share > 1 ? cu_share : tune(TUNE_CU_SHARE);
-    if (share > 1) ncu = (ncu / share + 7) / 8 * 8;
+    const int ncu = share > 1 ? (device_cu / share + 7) / 8 * 8 : device_cu;
     // short K, tall shared activation (C = 320 / 640 levels): the row-stationary engine (aid_gemm_rs.hip) — the activation rows stay in
     // registers, the weights stream through LDS; it writes transposed problems itself.  GEMM_RS: 0 never, 1 wherever the shape allows.
-    {
-        const int rs = tune(TUNE_GEMM_RS);
-        // (the size rule looks at the DEVICE's CU count, not at the share the caller's hint leaves: the engine choice between this engine
-        //  and the tile engines — whose summation orders differ — must not depend on cu_share; only the split of the slice range does)
-        if (rs != 0 && force < 0 && gemm_rs_supported(g, num_cu(), rs == 1)) {
-            if (dry) { *is_ppx = true; return hipSuccess; }           // (a transposed problem stays as it is)
-            if (variant) *variant = g.p[0].k == 640 ? "rowstat640" : "rowstat320";
-            return gemm_rs_launch(g, std::is_same<T, f16>::value ? AID_DTYPE_F16 : AID_DTYPE_BF16, ncu, stream);
-        }
-    }
-    bool pp = false;
-    PpPlan pl = {};
-    GemmSide sd;
-    memset(&sd, 0, sizeof(sd));
+    // (the size rule looks at the DEVICE's CU count, not at the share the caller's hint leaves: the engine choice between this engine
+    //  and the tile engines — whose summation orders differ — must not depend on cu_share; only the split of the slice range does)
+    const int rs = tune(TUNE_GEMM_RS);
+    if (rs != 0 && force < 0 && gemm_rs_supported(g, device_cu, rs == 1)) return make_plan(GemmEngine::Rowstat, g, sd, ncu);
     if (g.interleave && g.n_problems > 1 && force != 7) {
         // K loops differ: if a few short problems (<= 15 % of the flops) sit next to main problems of ONE K that the
         // ping-pong engine would win, run the short ones as side tiles of the ping-pong launch
@@ -1789,54 +1652,38 @@ static hipError_t launch_gemm_sel(GemmGroup& g, hipStream_t stream, const char**
         for (int i = ns; i <= 4; ++i) sd.tile_start[i] = st;
         if (ok && ns > 0 && side_fl <= 0.15 * tot && st <= ncu) {
             const int nk = kmain / 64;
-            const int t128 = plan_tiles(gm, 128, 128);
-            const PpPlan plm = plan_pp(gm, ncu, nk);
+            const int t128 = count_tiles(gm, 128, 128);
+            const PpSplit sp = split_pp(count_tiles(gm, 256, 256), ncu, nk);
             const double r128 = 0.5 * (double)((2 * t128 + 2 * ncu - 1) / (2 * ncu));
-            if (5.0 + plm.rounds * (6.0 + 1.62 * nk) < 0.95 * (3.0 + r128 * (4.1 + 1.09 * nk)) || force == 31) {
+            if (5.0 + sp.rounds * (6.0 + 1.62 * nk) < 0.95 * (3.0 + r128 * (4.1 + 1.09 * nk)) || force == 31) {
                 sd.n = ns;
                 sd.tiles = st;
                 sd.pad_tiles = (st + 7) / 8 * 8;
-                if (prefer_ppx(gm, ncu, plm)) {
-                    if (dry) {                              // side tiles run on the 128 x 128 engine: no transposed output there
-                        *is_ppx = true;
-                        for (int i = 0; i < ns; ++i) *is_ppx = *is_ppx && !sd.p[i].trans_rows;
-                        return hipSuccess;
-                    }
-                    if (variant) *variant = "pingpong288+side128";
-                    return launch_ppx<T>(gm, stream, sd);
-                }
-                if (dry) return hipSuccess;
-                plan_pp(gm, ncu, nk);                       // back to 256 x 256 tile units
-                if (variant) *variant = plm.n_small ? "pingpong256+tail128+side128" : "pingpong256+side128";
-                return launch_pp<T>(gm, stream, plm, sd);
+                if (prefer_ppx(gm, ncu, sp.rounds)) return make_plan(GemmEngine::Pp288, gm, sd, ncu);
+                return make_plan(sp.n_small ? GemmEngine::Pp256Tail : GemmEngine::Pp256, gm, sd, ncu, sp.n_big, sp.n_small);
             }
         }
         memset(&sd, 0, sizeof(sd));
     }
+    bool pp = false;
+    PpSplit sp = {};
     if (!g.interleave && g.n_problems > 0) {
         const int nk = g.p[0].k / 64;
-        const int t128 = plan_tiles(g, 128, 128);
-        pl = plan_pp(g, ncu, nk);                   // last: leaves g.tile_start in 256 x 256 units for launch_pp
+        const int t128 = count_tiles(g, 128, 128), t256 = count_tiles(g, 256, 256);
+        sp = split_pp(t256, ncu, nk);
         const double r128 = 0.5 * (double)((2 * t128 + 2 * ncu - 1) / (2 * ncu));       // rounds of 2 CUs-fulls, in halves
         const double cost_ls = 3.0 + r128 * (4.1 + 1.09 * nk);
         // (a single round that leaves CUs idle runs its tiles faster — less contention for L2 / HBM, a higher clock: measured 35.5 us at
         //  160 of 256 tiles, 41.3 at 240, 43.4 modelled for a full round, K = 1280; profiles/r05_gemm_shards_ab.txt)
-        const int pp_tiles = pl.n_small ? 0 : pl.tiles;
+        const int pp_tiles = sp.n_small ? 0 : t256;
         const double occ = (pp_tiles > 0 && pp_tiles <= ncu) ? (double)pp_tiles / ncu : 1.0;
-        const double cost_pp = 5.0 + pl.rounds * (6.0 + 1.62 * nk) * (0.65 + 0.35 * occ);
+        const double cost_pp = 5.0 + sp.rounds * (6.0 + 1.62 * nk) * (0.65 + 0.35 * occ);
         pp = cost_pp < 0.95 * cost_ls;
         if (force == 31) pp = true;
     }
     if (force == 7) pp = false;
-    if (pp && prefer_ppx(g, ncu, pl)) {
-        if (dry) { *is_ppx = true; return hipSuccess; }
-        if (variant) *variant = "pingpong288";
-        return launch_ppx<T>(g, stream, sd);
-    }
-    if (dry) return hipSuccess;
-    if (pp) plan_pp(g, ncu, g.p[0].k / 64);             // g.tile_start back in 256 x 256 units
-    if (variant) *variant = !pp ? "lockstep128" : pl.n_small ? "pingpong256+tail128" : "pingpong256";
-    if (pp) return launch_pp<T>(g, stream, pl, sd);
+    if (pp && prefer_ppx(g, ncu, sp.rounds)) return make_plan(GemmEngine::Pp288, g, sd, ncu);
+    if (pp) return make_plan(sp.n_small ? GemmEngine::Pp256Tail : GemmEngine::Pp256, g, sd, ncu, sp.n_big, sp.n_small);
     // 8 waves, 64 x 32 wave tiles.  The ring: a K tile's loads are in flight for ~0.75 us whatever the launch (HBM / L2 latency), so a
     // workgroup that is alone on its CU with ONE tile ahead is latency-bound (0.75 us per K tile against 0.24 us of MFMAs).
     // Measured (profiles/r06_gemm_lockstep_rings.txt): a K tile step costs 0.5 - 0.65 us with one tile ahead and ~0.5 with three ahead —
@@ -1846,16 +1693,55 @@ static hipError_t launch_gemm_sel(GemmGroup& g, hipStream_t stream, const char**
     // (32-wide K tiles — four stages in 64 KB, or three in 48 KB for three workgroups per CU — lost everywhere: same file.)
     int ls = tune(TUNE_GEMM_LS);
     if (ls < 0) {
-        const int t128 = plan_tiles(g, 128, 128);
+        const int t128 = count_tiles(g, 128, 128);
         int nk_min = 1 << 30;
         for (int i = 0; i < g.n_problems; ++i) nk_min = g.p[i].k / 64 < nk_min ? g.p[i].k / 64 : nk_min;
-        ls = (t128 >= 64 && t128 <= num_cu() && nk_min >= 16) ? 1 : 0;
+        ls = (t128 >= 64 && t128 <= device_cu && nk_min >= 16) ? 1 : 0;
     }
-    if (ls == 1) { if (variant) *variant = "lockstep128x4"; return launch_pipe<T, 128, 128, 64, 4, 2, 4>(g, stream); }
-    return launch_pipe<T, 128, 128, 64, 2, 2, 4>(g, stream);       // 2 workgroups / CU
+    return make_plan(ls == 1 ? GemmEngine::Lockstep4 : GemmEngine::Lockstep, g, sd, ncu);     // Lockstep: 2 workgroups / CU
 }
 
-hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant, int cu_share) {
+template <typename T>
+static hipError_t launch_plan(GemmPlan& pl, hipStream_t stream) {
+    switch (pl.engine) {
+        case GemmEngine::Edge:      return launch_edge<T>(pl.g, stream);
+        case GemmEngine::Lockstep:  return launch_pipe<T, 2>(pl.g, stream);
+        case GemmEngine::Lockstep4: return launch_pipe<T, 4>(pl.g, stream);
+        case GemmEngine::Pp256:
+        case GemmEngine::Pp256Tail: return launch_pp<T>(pl.g, stream, pl.n_big, pl.n_small, pl.sd);
+        case GemmEngine::Pp288:     return launch_ppx<T>(pl.g, stream, pl.sd);
+        case GemmEngine::Rowstat:   return gemm_rs_launch(pl.g, std::is_same<T, f16>::value ? AID_DTYPE_F16 : AID_DTYPE_BF16, pl.ncu, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// A problem with trans_rows (C transposed per frame, the flat value projection E Wv^T -> V^T) runs as such only where the planned
+// engine writes transposed C (GemmPlan.writes_trans).  Everywhere else it is rewritten into the equivalent batched product with swapped
+// operands, V^T[f] = Wv E_f^T  (m' = n channels, n' = trans_rows keys, one batch entry per frame) — what the callers issued before —
+// and the rewritten group is planned again.
+static bool has_trans(const GemmGroup& g) {
+    for (int i = 0; i < g.n_problems; ++i)
+        if (g.p[i].trans_rows) return true;
+    return false;
+}
+static void untranspose(GemmGroup& g) {
+    for (int i = 0; i < g.n_problems; ++i) {
+        GemmDesc& d = g.p[i];
+        if (!d.trans_rows) continue;
+        const int rows = d.trans_rows, frames = d.m / rows;
+        GemmDesc o = d;
+        o.a = d.b; o.b = d.a;
+        o.m = d.n; o.n = rows;
+        o.lda = d.ldb; o.ldb = d.lda;
+        o.batch = frames;
+        o.stride_a = 0; o.stride_b = (int64_t)rows * d.lda;      // stride_c = frame stride of V^T already
+        if (d.ln_stats) { o.ln_side = 2; o.stride_stats = rows; }
+        o.trans_rows = 0;
+        d = o;
+    }
+}
+
+hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant, const char** symbol, int cu_share) {
     // Longest K loop first: blocks are dispatched in grid order, so the tiles that take longest (the K = 2048
     // text-context projections of a cross-attention layer next to its K = 1280 query projection) start first
     // and finish under the rest instead of forming the tail of the launch (measured: 107 -> 7x us).
@@ -1868,7 +1754,16 @@ hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const 
             g.p[j] = g.p[j - 1];
             g.p[j - 1] = t;
         }
-    return dtype == AID_DTYPE_F16 ? launch_gemm<f16>(g, stream, variant, cu_share) : launch_gemm<bf16>(g, stream, variant, cu_share);
+    const int device_cu = num_cu();
+    if (device_cu <= 0) return hipErrorInvalidDevice;
+    GemmPlan pl = plan_gemm(g, device_cu, cu_share);
+    if (has_trans(g) && !pl.writes_trans) {
+        untranspose(g);
+        pl = plan_gemm(g, device_cu, cu_share);
+    }
+    if (variant) *variant = pl.variant;
+    if (symbol) *symbol = pl.symbol;
+    return dtype == AID_DTYPE_F16 ? launch_plan<f16>(pl, stream) : launch_plan<bf16>(pl, stream);
 }
 
 }  // namespace aid

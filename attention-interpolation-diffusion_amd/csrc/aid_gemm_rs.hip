@@ -395,17 +395,11 @@ __global__ __launch_bounds__(NW * 64) void aid_gemm_rs_kernel(const RsParams p) 
 
 template <typename T, int K, int NW, int VAR = 0>
 static hipError_t rs_launch(const RsParams& p, hipStream_t stream) {
-    static PerDevice<bool> attr_set;
+    static PerDevice<int> attr_set;
     constexpr size_t smem = (size_t)RS_NSTG * 32 * K * 2 + (size_t)RS_BIASN * 2;
     static_assert(smem <= 160 * 1024, "one workgroup's LDS");
-    bool* done = attr_set.slot();
-    if (!done) return hipErrorInvalidDevice;
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(aid_gemm_rs_kernel<T, K, NW, VAR>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        *done = true;
-    }
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(aid_gemm_rs_kernel<T, K, NW, VAR>), smem);
+    if (e != hipSuccess) return e;
     const int grid = (p.m / (32 * NW)) * p.nsplit;
     hipLaunchKernelGGL((aid_gemm_rs_kernel<T, K, NW, VAR>), dim3(grid), dim3(NW * 64), smem, stream, p);
     return hipGetLastError();

@@ -50,7 +50,7 @@ struct GemmSide {
 // aid_set_tuning() — same-process A/B runs flip a knob between launches.  -1 = unset (the launch heuristics decide).
 enum Tune {
     TUNE_GEMM_VARIANT = 0,      // 7 = force the lock-step engine, 31 = force the ping-pong engine
-    TUNE_GEMM_PP,               // ping-pong K loop: 0 = DMA issued between the MFMAs, 1 = in the read slot, 2 = 1 + s_setprio, 3 = 0 + s_setprio
+    TUNE_GEMM_PP,               // ping-pong K loop: 0 = DMA issued between the MFMAs, 1 = in the read slot, 2 = 1 + s_setprio; 3 = the default (1)
     TUNE_GEMM_TRI,              // 0 = never use the twelve-wave 288 x 256 engine, 1 = force it where the shape allows
     TUNE_ATTN_NW,               // 4 / 8 waves per workgroup
     TUNE_ATTN_QB,               // 1 / 2 query blocks per wave (d = 40 PLAIN)
@@ -71,9 +71,10 @@ enum Tune {
 };
 int tune(int id);
 
-// picks the tile shape, fills g.tile_start and launches
+// picks the engine and launches it; `variant` / `symbol` receive the engine's name and its kernel symbol
 // cu_share > 1: the caller runs that many launch streams side by side (AidGemmProblem.cu_share); 0 / 1: the process-wide CU_SHARE knob decides
-hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant = nullptr, int cu_share = 0);
+hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant = nullptr, const char** symbol = nullptr,
+                             int cu_share = 0);
 
 // row-stationary engine (aid_gemm_rs.hip): K = 320 / 640, one shared tall activation; `ncu` = CUs the launch may count on
 bool       gemm_rs_supported(const GemmGroup& g, int ncu, bool ignore_size);
