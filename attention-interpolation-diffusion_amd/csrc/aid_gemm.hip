@@ -252,6 +252,11 @@ __global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel(const GemmGroup g
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = (n + e < P.n) ? r0[e] + (float)R[e] : 0.f;
                 }
+                // columns [n, round_up(n, 4)) are written with zeros (aid_hip.h): the guarded loads leave their accumulators 0, but the
+                // folded LayerNorm's fix-up (or a negative scale) does not keep them there
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n + e >= P.n) v[e] = 0.f;
                 *reinterpret_cast<T4*>(C + (int64_t)m * P.ldc + n) = cvt4<T>(v);
             }
         }
@@ -648,10 +653,13 @@ struct Engine {
                     v = cvt8<T>(a + b);
                 }
                 *reinterpret_cast<T8*>(dst) = v;
-            } else {
+            } else {                                // the chunk of the last column: [P.n, round_up(P.n, 4)) gets zeros (aid_hip.h)
+                const int n4 = (P.n + 3) & ~3;
 #pragma unroll
-                for (int e = 0; e < 8; ++e)
+                for (int e = 0; e < 8; ++e) {
                     if (n + e < P.n) dst[e] = res ? (T)((float)v[e] + (float)res[e]) : v[e];
+                    else if (n + e < n4) dst[e] = (T)0.f;
+                }
             }
         }
     }
@@ -1282,10 +1290,13 @@ struct PingPongX : PingPong<T> {
                     v = cvt8<T>(a + b);
                 }
                 *reinterpret_cast<T8*>(dst) = v;
-            } else {
+            } else {                                // the chunk of the last column: [P.n, round_up(P.n, 4)) gets zeros (aid_hip.h)
+                const int n4 = (P.n + 3) & ~3;
 #pragma unroll
-                for (int e = 0; e < 8; ++e)
+                for (int e = 0; e < 8; ++e) {
                     if (n + e < P.n) dst[e] = res ? (T)((float)v[e] + (float)res[e]) : v[e];
+                    else if (n + e < n4) dst[e] = (T)0.f;
+                }
             }
         }
     }

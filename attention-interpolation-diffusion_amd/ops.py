@@ -351,7 +351,8 @@ def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: 
     vt = torch.empty(f + extra_rows, c, lp, dtype=e.dtype, device=e.device)
     if l % 8 == 0:          # flat value projection, transposed epilogue (tile count of the key projection: whole CU rounds)
         pv = dict(a=e, b=wv, c=vt, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=lp, stride_c=c * lp, trans_rows=l)
-    else:                   # V^T[f] = Wv E_f^T, one batch entry per frame (pad columns l .. lp of V^T are written with zeros)
+    else:                   # V^T[f] = Wv E_f^T, one batch entry per frame.  Pad columns l .. round_up(l, 4) of V^T are written with
+        #                     zeros (aid_hip.h); round_up(l, 4) .. lp are not written, and the attention kernels do not read their values
         pv = dict(a=wv, b=e, c=vt, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=lp, batch=f, stride_a=0, stride_b=l * cc, stride_c=c * lp)
     gemm_nt([dict(a=e, b=wk, c=k, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c), pv])
     return k, vt

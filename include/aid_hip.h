@@ -207,7 +207,9 @@ int aid_attn_fwd(const AidAttnArgs* args /* host */, void* stream);
  *   k2[i] = (1 - coef[i]) * k[begin] + coef[i] * k[end]     (and the same for vt -> vt2)
  * for every frame i with 0 < coef[i] < 1 (other frames are left untouched: the attention kernel reads
  * the end-point frames themselves).  k_fs / vt_fs are the frame strides in elements (multiples of 8)
- * of all four tensors.  One streaming launch. */
+ * of all four tensors.  The WHOLE stride of such a frame is written — k2[i * k_fs .. (i + 1) * k_fs) and
+ * vt2[i * vt_fs .. (i + 1) * vt_fs), gap rows and V^T pad columns included, lerped from whatever k / vt
+ * hold there — and all of k[begin], k[end], vt[begin], vt[end] is read.  One streaming launch. */
 int aid_lerp_kv(const void* k, const void* vt, void* k2, void* vt2, const float* coef /* device */,
                 int32_t n_frames, int32_t begin, int32_t end, int64_t k_fs, int64_t vt_fs, int32_t dtype,
                 void* stream);

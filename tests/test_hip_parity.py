@@ -124,8 +124,11 @@ def test_grouped_gemm_randomized_shapes_both_engines(tuning):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids_dt)
-@pytest.mark.parametrize("shape", [(3, 77, 96, 80), (7, 200, 64, 128), (2, 5, 8, 40)])
-def test_kv_projection_writes_transposed_values_and_zero_padding(dtype, shape):
+@pytest.mark.parametrize("shape", [(3, 77, 96, 80), (7, 200, 64, 128), (2, 5, 8, 40), (3, 77, 768, 320), (2, 77, 2048, 640)])
+def test_kv_projection_writes_transposed_values_and_zero_padding(dtype, shape, tuning):
+    """project_kv's keys and V^T against fp64, and the V^T padding: the problems it issues, run through gemm_nt into a NaN-filled
+    V^T, leave columns [l, round_up(l, 4)) exactly zero (aid_hip.h) on the edge engine (K % 64 != 0) and on the tile engines
+    (K = 768 / 2048, ragged l = 77: the cross-attention text projections), with the tile engines forced in turn."""
     f, l, cc, c = shape
     g = torch.Generator().manual_seed(l)
     e = torch.randn(f, l, cc, generator=g).to(dtype)
@@ -134,9 +137,27 @@ def test_kv_projection_writes_transposed_values_and_zero_padding(dtype, shape):
     k, vt = ops.project_kv(e.to(DEV), wk.to(DEV), wv.to(DEV))
     assert vt.shape == (f, c, (l + 7) // 8 * 8)
     assert rel_l2(to_np64(k), to_np64(e) @ to_np64(wk).T) < TOL_GEMM[dtype]
-    assert rel_l2(to_np64(vt[:, :, :l]), (to_np64(e) @ to_np64(wv).T).transpose(0, 2, 1)) < TOL_GEMM[dtype]
-    lp4 = (l + 3) // 4 * 4
+    ref_vt = (to_np64(e) @ to_np64(wv).T).transpose(0, 2, 1)
+    assert rel_l2(to_np64(vt[:, :, :l]), ref_vt) < TOL_GEMM[dtype]
     assert torch.isfinite(vt[:, :, :l].float()).all()
+    lp, lp4 = (l + 7) // 8 * 8, (l + 3) // 4 * 4
+    ed, wkd, wvd = e.to(DEV), wk.to(DEV), wv.to(DEV)
+    for knobs in ([], [("GEMM_VARIANT", 7), ("GEMM_LS", 0)], [("GEMM_VARIANT", 31), ("GEMM_TRI", 0)], [("GEMM_VARIANT", 31), ("GEMM_TRI", 1)]):
+        if knobs and cc % 64:
+            continue                                                  # (K % 64 != 0 runs on the edge engine only)
+        for name, value in knobs:
+            tuning(name, value)
+        kk = torch.empty(f, l, c, dtype=dtype, device=DEV)
+        vv = torch.full((f, c, lp), float("nan"), dtype=dtype, device=DEV)
+        if l % 8 == 0:      # the same two problems project_kv issues
+            pv = dict(a=ed, b=wvd, c=vv, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=lp, stride_c=c * lp, trans_rows=l)
+        else:
+            pv = dict(a=wvd, b=ed, c=vv, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=lp, batch=f, stride_a=0, stride_b=l * cc, stride_c=c * lp)
+        ops.gemm_nt([dict(a=ed, b=wkd, c=kk, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c), pv])
+        variant = ops.last_gemm_variant()
+        assert torch.equal(vv[:, :, :l], vt[:, :, :l]) or knobs, variant
+        assert rel_l2(to_np64(vv[:, :, :l]), ref_vt) < TOL_GEMM[dtype], variant
+        assert (vv[:, :, l:lp4].view(torch.int16) == 0).all(), (variant, "V^T pad columns [l, round_up(l, 4)) not +0")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1025,9 +1046,9 @@ def test_gemm_side_problems_ride_in_the_pingpong_launch(dtype):
     xd, ed, ipd, wqd, wkd, wvd, wkid, wvid = map(d, (x, e, ip, wq, wk, wv, wki, wvi))
     q = torch.empty(n * s, c, dtype=dtype, device=DEV)
     k = torch.empty(nctx, l, c, dtype=dtype, device=DEV)
-    vt = torch.zeros(nctx, c, 80, dtype=dtype, device=DEV)
+    vt = torch.full((nctx, c, 80), float("nan"), dtype=dtype, device=DEV)      # the pad columns must be WRITTEN with zeros
     kip = torch.empty(nctx, t_ip, c, dtype=dtype, device=DEV)
-    vtip = torch.zeros(nctx, c, 8, dtype=dtype, device=DEV)
+    vtip = torch.full((nctx, c, 8), float("nan"), dtype=dtype, device=DEV)
     probs = [dict(a=xd, b=wqd, c=q, m=n * s, n=c, k=c, lda=c, ldb=c, ldc=c),
              dict(a=ed, b=wkd, c=k, m=nctx * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c),
              dict(a=wvd, b=ed, c=vt, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=80, batch=nctx, stride_a=0, stride_b=l * cc, stride_c=c * 80),
