@@ -15,7 +15,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AID_LIB_PATH") or os.path.join(PKG_DIR, "libaid_hip.so")   # override: development A/B builds
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 
-AID_ABI_VERSION = 8
+AID_ABI_VERSION = 9
 DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 0, 1, 2
 MODE_PLAIN, MODE_INNER, MODE_OUTER = 0, 1, 2
 GEMM_MAX_PROBLEMS = 6
@@ -40,6 +40,8 @@ class AidGemmProblem(C.Structure):
         ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p), ("ln_shift", C.c_void_p),
         ("ln_side", C.c_int32), ("trans_rows", C.c_int32), ("stride_stats", C.c_int64),
         ("cu_share", C.c_int32), ("reserved0", C.c_int32),
+        ("lr_a", C.c_void_p), ("lr_b", C.c_void_p), ("lr_k", C.c_int32), ("lr_lda", C.c_int32), ("lr_ldb", C.c_int32),
+        ("reserved1", C.c_int32), ("lr_stride_a", C.c_int64), ("lr_stride_b", C.c_int64),
     ]
 
 
@@ -80,6 +82,9 @@ class AidProcessorArgs(C.Structure):
         ("k_cached", C.c_void_p), ("vt_cached", C.c_void_p),
         ("cu_share", C.c_int32), ("reserved1", C.c_int32),
         ("attn_bias", C.c_void_p), ("attn_bias_fs", C.c_int64), ("attn_bias_hs", C.c_int32), ("attn_bias_rs", C.c_int32),
+        ("lora_down_x", C.c_void_p), ("lora_down_ctx", C.c_void_p), ("lora_down_o", C.c_void_p),
+        ("lora_up_q", C.c_void_p), ("lora_up_k", C.c_void_p), ("lora_up_v", C.c_void_p), ("lora_up_o", C.c_void_p),
+        ("lora_r_q", C.c_int32), ("lora_r_k", C.c_int32), ("lora_r_v", C.c_int32), ("lora_r_o", C.c_int32),
     ]
 
 

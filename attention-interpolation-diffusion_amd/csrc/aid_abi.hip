@@ -119,12 +119,19 @@ int check_problem(const AidGemmProblem& q) {
         if (q.batch != 1 || q.bias || q.residual || q.m % q.trans_rows || (q.ln_stats && q.ln_side != 1)) return AID_ERR_ARG;
         if (q.trans_rows % 8 || q.ldc % 8 || q.ldc < q.trans_rows || q.stride_c % 8) return AID_ERR_SHAPE;
     }
+    if (q.lr_k < 0) return AID_ERR_ARG;
+    if (q.lr_k > 0) {                                    // low-rank second K segment (ABI v9)
+        if (!q.lr_a || !q.lr_b || q.ln_stats) return AID_ERR_ARG;      // the folded LayerNorm's correction would scale the term too
+        if (q.lr_k % 64 || q.lr_k > 512 || q.lr_lda % 8 || q.lr_ldb % 8 || q.lr_lda < q.lr_k || q.lr_ldb < q.lr_k) return AID_ERR_SHAPE;
+        if (q.lr_stride_a % 8 || q.lr_stride_b % 8 || !aligned16(q.lr_a) || !aligned16(q.lr_b)) return AID_ERR_SHAPE;
+    }
     return AID_OK;
 }
 
 struct Carve {
-    size_t q, k, vt, o, k2, vt2, xn, kip, vtip, total;
+    size_t q, k, vt, o, k2, vt2, xn, kip, vtip, ux, uctx, uo, total;
     int lp, tp;
+    int rx, rctx;                                         // LoRA: columns of U of x / of ctx
 };
 
 Carve carve(const AidProcessorArgs& a) {
@@ -152,6 +159,12 @@ Carve carve(const AidProcessorArgs& a) {
         c.kip = off;  off += align_up((size_t)a.n_ip * a.t_ip * a.c * es, 256);
         c.vtip = off; off += align_up((size_t)a.n_ip * a.c * c.tp * es, 256);
     }
+    c.ux = c.uctx = c.uo = off;                           // LoRA: U = input A_pack^T of x (q [k v]), ctx (k v) and o
+    c.rx = a.lora_r_q + (a.ctx ? 0 : a.lora_r_k + a.lora_r_v);
+    c.rctx = a.ctx ? a.lora_r_k + a.lora_r_v : 0;
+    if (c.rx) { c.ux = off; off += align_up((size_t)a.n_frames * a.s * c.rx * es, 256); }
+    if (c.rctx) { c.uctx = off; off += align_up((size_t)a.n_ctx * a.l * c.rctx * es, 256); }
+    if (a.lora_r_o) { c.uo = off; off += align_up((size_t)a.n_frames * a.s * a.lora_r_o * es, 256); }
     c.total = off;
     return c;
 }
@@ -196,6 +209,26 @@ int check_processor(const AidProcessorArgs& a) {
             if (!a.ln_const || a.c % 64 || !aligned16(a.ln_wq)) return AID_ERR_SHAPE;
             if (!a.ctx && (!a.ln_wk || !a.ln_wv || !aligned16(a.ln_wk) || !aligned16(a.ln_wv))) return AID_ERR_ARG;
         }
+    }
+    // LoRA (ABI v9): ranks are multiples of 64 up to 512; every projection with a rank needs its up weights and its stacked down weights
+    const int32_t ranks[4] = {a.lora_r_q, a.lora_r_k, a.lora_r_v, a.lora_r_o};
+    const void* ups[4] = {a.lora_up_q, a.lora_up_k, a.lora_up_v, a.lora_up_o};
+    bool any = false;
+    for (int i = 0; i < 4; ++i) {
+        if (ranks[i] < 0) return AID_ERR_ARG;
+        if (!ranks[i]) continue;
+        any = true;
+        if (ranks[i] % 64 || ranks[i] > 512) return AID_ERR_SHAPE;
+        if (!ups[i] || !aligned16(ups[i])) return AID_ERR_ARG;
+    }
+    if (any) {
+        if (a.ln_wq) return AID_ERR_ARG;            // the folded LayerNorm's correction would scale the low-rank term too
+        if (a.k_cached && (a.lora_r_k || a.lora_r_v)) return AID_ERR_ARG;     // cached keys must already hold the adapter term
+        const bool need_x = a.lora_r_q || (!a.ctx && (a.lora_r_k || a.lora_r_v));
+        const bool need_ctx = a.ctx && (a.lora_r_k || a.lora_r_v);
+        if ((need_x && (!a.lora_down_x || !aligned16(a.lora_down_x))) || (need_ctx && (!a.lora_down_ctx || !aligned16(a.lora_down_ctx))) ||
+            (a.lora_r_o && (!a.lora_down_o || !aligned16(a.lora_down_o))))
+            return AID_ERR_ARG;
     }
     return AID_OK;
 }
@@ -311,10 +344,19 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
     aid::GemmGroup g;
     memset(&g, 0, sizeof(g));
     g.n_problems = n_problems;
+    aid::GemmLR lr;
+    memset(&lr, 0, sizeof(lr));
+    bool has_lr = false;
     for (int i = 0; i < n_problems; ++i) {
         const AidGemmProblem& q = problems[i];
         int rc = check_problem(q);
         if (rc != AID_OK) return rc;
+        if (q.lr_k > 0) {
+            aid::GemmLRDesc& L = lr.p[i];
+            L.a = q.lr_a; L.b = q.lr_b; L.k = q.lr_k; L.lda = q.lr_lda; L.ldb = q.lr_ldb;
+            L.stride_a = q.lr_stride_a; L.stride_b = q.lr_stride_b;
+            has_lr = true;
+        }
         aid::GemmDesc& d = g.p[i];
         d.a = q.a; d.b = q.b; d.c = q.c; d.bias = q.bias; d.residual = q.residual;
         d.m = q.m; d.n = q.n; d.k = q.k;
@@ -333,23 +375,27 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
     if (g_prof_on.load(std::memory_order_relaxed)) {
         for (int i = 0; i < n_problems; ++i) {
             const AidGemmProblem& q = problems[i];
-            flops += 2.0 * q.m * q.n * q.k * q.batch;
+            flops += 2.0 * q.m * q.n * ((double)q.k + q.lr_k) * q.batch;
             bytes += 2.0 * ((double)q.m * q.k * (q.stride_a || q.batch == 1 ? q.batch : 1) +
                             (double)q.n * q.k * (q.stride_b || q.batch == 1 ? q.batch : 1) +
                             (double)q.m * q.n * q.batch * (q.residual ? 2 : 1));
+            if (q.lr_k > 0)
+                bytes += 2.0 * ((double)q.m * q.lr_k * (q.lr_stride_a || q.batch == 1 ? q.batch : 1) +
+                                (double)q.n * q.lr_k * (q.lr_stride_b || q.batch == 1 ? q.batch : 1));
         }
     }
     hipError_t e;
     {
         ProfScope ps(static_cast<hipStream_t>(stream), "aid_gemm_nt", flops, dtype == AID_DTYPE_F32 ? 2.0 * bytes : bytes);
         if (dtype == AID_DTYPE_F32) {
-            e = aid::gemm_f32_launch(g, static_cast<hipStream_t>(stream));
+            e = aid::gemm_f32_launch(g, static_cast<hipStream_t>(stream), has_lr ? &lr : nullptr);
             g_gemm_variant = "f32";
-            ps.rename("aid_gemm_f32_kernel");
+            ps.rename(has_lr ? "aid_gemm_f32_kernel_lr" : "aid_gemm_f32_kernel");
         } else {
             // profile entries carry the kernel SYMBOL that ran, so they line up with rocprofv3's per-kernel rows
             const char* sym = "aid_gemm_nt_kernel";
-            e = aid::gemm_group_launch(g, dtype, static_cast<hipStream_t>(stream), &g_gemm_variant, &sym, problems[0].cu_share);
+            e = aid::gemm_group_launch(g, dtype, static_cast<hipStream_t>(stream), &g_gemm_variant, &sym, problems[0].cu_share,
+                                       has_lr ? &lr : nullptr);
             char nm[64];
             snprintf(nm, sizeof(nm), "%s<%s>", sym, dtype_name(dtype));
             ps.rename(nm);
@@ -551,6 +597,32 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
     const int l = cross ? a.l : a.s;
     const int cc = cross ? a.cc : a.c;
     const int d = a.c / a.heads;
+    const size_t es = a.dtype == AID_DTYPE_F32 ? 4 : 2;
+
+    // 0b. LoRA (ABI v9): U = input A_pack^T of x (q [, k, v]) and of ctx (k, v) in one grouped launch; the projections below add
+    //     U B_pack^T to their accumulators (AidGemmProblem.lr_*)
+    char* ux = ws + cv.ux;
+    char* uctx = ws + cv.uctx;
+    if (cv.rx || cv.rctx) {
+        AidGemmProblem pd[2];
+        memset(pd, 0, sizeof(pd));
+        int nd = 0;
+        if (cv.rx) {
+            pd[nd].a = xin; pd[nd].b = a.lora_down_x; pd[nd].c = ux;
+            pd[nd].m = a.n_frames * a.s; pd[nd].n = cv.rx; pd[nd].k = a.c;
+            pd[nd].lda = a.c; pd[nd].ldb = a.c; pd[nd].ldc = cv.rx; pd[nd].batch = 1;
+            ++nd;
+        }
+        if (cv.rctx) {
+            pd[nd].a = a.ctx; pd[nd].b = a.lora_down_ctx; pd[nd].c = uctx;
+            pd[nd].m = a.n_ctx * a.l; pd[nd].n = cv.rctx; pd[nd].k = a.cc;
+            pd[nd].lda = a.cc; pd[nd].ldb = a.cc; pd[nd].ldc = cv.rctx; pd[nd].batch = 1;
+            ++nd;
+        }
+        pd[0].cu_share = a.cu_share;
+        rc = aid_gemm_nt(pd, nd, a.dtype, stream);
+        if (rc != AID_OK) return rc;
+    }
 
     // 1. q, k and V^T projections in one grouped launch
     AidGemmProblem pr[5];
@@ -586,6 +658,29 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
             pr[2].ln_stats = stats; pr[2].ln_colsum = a.ln_const + 4 * a.c; pr[2].ln_shift = a.ln_const + 5 * a.c;
             if (pr[2].trans_rows) { pr[2].b = a.ln_wv; pr[2].ln_side = 1; }
             else                  { pr[2].a = a.ln_wv; pr[2].ln_side = 2; pr[2].stride_stats = l; }
+        }
+    }
+    if (a.lora_r_q) {
+        pr[0].lr_a = ux; pr[0].lr_lda = cv.rx;
+        pr[0].lr_b = a.lora_up_q; pr[0].lr_ldb = a.lora_r_q; pr[0].lr_k = a.lora_r_q;
+    }
+    {
+        char* ue = cross ? uctx : ux;                         // U of the keys' / values' input, its columns, and where k / v start
+        const int re = cross ? cv.rctx : cv.rx;
+        const size_t ok = cross ? 0 : (size_t)a.lora_r_q, ov = ok + a.lora_r_k;
+        if (a.lora_r_k) {
+            pr[1].lr_a = ue + ok * es; pr[1].lr_lda = re;
+            pr[1].lr_b = a.lora_up_k; pr[1].lr_ldb = a.lora_r_k; pr[1].lr_k = a.lora_r_k;
+        }
+        if (a.lora_r_v) {
+            pr[2].lr_k = a.lora_r_v;
+            if (pr[2].trans_rows) {                           // flat x Wv^T: LA = U_v (rows like x), LB = B_v
+                pr[2].lr_a = ue + ov * es; pr[2].lr_lda = re;
+                pr[2].lr_b = a.lora_up_v; pr[2].lr_ldb = a.lora_r_v;
+            } else {                                          // V^T[f] = Wv E_f^T: LA = B_v (shared), LB = U_v[f]
+                pr[2].lr_a = a.lora_up_v; pr[2].lr_lda = a.lora_r_v;
+                pr[2].lr_b = ue + ov * es; pr[2].lr_ldb = re; pr[2].lr_stride_b = (int64_t)l * re;
+            }
         }
     }
     int npr = 3;
@@ -657,13 +752,25 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
         if (rc != AID_OK) return rc;
     }
 
-    // 3. out projection + bias
+    // 3. out projection + bias (LoRA on to_out: U_o = o A_o^T first)
     AidGemmProblem po;
     memset(&po, 0, sizeof(po));
     po.a = o; po.b = a.wo; po.c = a.y; po.bias = a.bo; po.residual = a.residual;
     po.m = a.n_frames * a.s; po.n = a.c; po.k = a.c;
     po.lda = a.c; po.ldb = a.c; po.ldc = a.c; po.batch = 1;
     po.cu_share = a.cu_share;
+    if (a.lora_r_o) {
+        AidGemmProblem pd;
+        memset(&pd, 0, sizeof(pd));
+        pd.a = o; pd.b = a.lora_down_o; pd.c = ws + cv.uo;
+        pd.m = a.n_frames * a.s; pd.n = a.lora_r_o; pd.k = a.c;
+        pd.lda = a.c; pd.ldb = a.c; pd.ldc = a.lora_r_o; pd.batch = 1;
+        pd.cu_share = a.cu_share;
+        rc = aid_gemm_nt(&pd, 1, a.dtype, stream);
+        if (rc != AID_OK) return rc;
+        po.lr_a = ws + cv.uo; po.lr_lda = a.lora_r_o;
+        po.lr_b = a.lora_up_o; po.lr_ldb = a.lora_r_o; po.lr_k = a.lora_r_o;
+    }
     return aid_gemm_nt(&po, 1, a.dtype, stream);
 }
 

@@ -263,6 +263,168 @@ __global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel(const GemmGroup g
     }
 }
 
+// The same tile with the problem's low-rank segment (GemmLR) run through a second K loop before the epilogue.  A copy on purpose:
+// with the kernel above turned into an instantiation of a shared template, its register allocation changed.
+template <typename T>
+__device__ __forceinline__ void gemm_edge_tile_lr(const GemmGroup& g, const GemmLR* lr) {
+    typedef typename Vec<T>::v8 T8;
+    typedef typename Vec<T>::v4 T4;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* As = reinterpret_cast<T*>(smem_raw);                 // [2][GBM][GLD]
+    T* Bs = As + 2 * GBM * GLD;                             // [2][GBN][GLD]
+
+    const TileCoord tc = locate_tile<GBM, GBN>(g, blockIdx.x, gridDim.x);
+    const GemmDesc& P = g.p[tc.p];
+    const int m0 = tc.m0, n0 = tc.n0;
+    const T* __restrict__ A = reinterpret_cast<const T*>(P.a) + (int64_t)tc.batch * P.stride_a;
+    const T* __restrict__ B = reinterpret_cast<const T*>(P.b) + (int64_t)tc.batch * P.stride_b;
+    T* __restrict__ C = reinterpret_cast<T*>(P.c) + (int64_t)tc.batch * P.stride_c;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;   // wave tile origin inside the block tile
+    const int l31 = lane & 31, hi = lane >> 5;
+
+    // staging: 128 rows x 8 chunks(16 B) per operand tile = 1024 chunks, 4 per thread
+    const int srow = tid >> 3, scol = (tid & 7) * 8;         // + 32 rows per step
+    T8 ra[4], rb[4];
+
+    auto stage_load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = srow + 32 * i;
+            const bool kin = (k0 + scol) < P.k;
+            ra[i] = (kin && (m0 + r) < P.m) ? *reinterpret_cast<const T8*>(A + (int64_t)(m0 + r) * P.lda + k0 + scol)
+                                            : zero8<T>();
+            rb[i] = (kin && (n0 + r) < P.n) ? *reinterpret_cast<const T8*>(B + (int64_t)(n0 + r) * P.ldb + k0 + scol)
+                                            : zero8<T>();
+        }
+    };
+    auto stage_write = [&](int buf) {
+        T* as = As + buf * GBM * GLD;
+        T* bs = Bs + buf * GBN * GLD;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = srow + 32 * i;
+            *reinterpret_cast<T8*>(as + r * GLD + scol) = ra[i];
+            *reinterpret_cast<T8*>(bs + r * GLD + scol) = rb[i];
+        }
+    };
+
+    f32x16 acc[2][2];   // [n block][m block]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // one K tile of MFMAs out of LDS buffer `buf`
+    auto mac_tile = [&](int buf) {
+        const T* as = As + buf * GBM * GLD + (wm + l31) * GLD + hi * 8;
+        const T* bs = Bs + buf * GBN * GLD + (wn + l31) * GLD + hi * 8;
+#pragma unroll
+        for (int ks = 0; ks < GBK / 16; ++ks) {
+            T8 fa[2], fb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fa[i] = *reinterpret_cast<const T8*>(as + i * 32 * GLD + ks * 16);   // rows m
+                fb[i] = *reinterpret_cast<const T8*>(bs + i * 32 * GLD + ks * 16);   // rows n
+            }
+#pragma unroll
+            for (int in = 0; in < 2; ++in)
+#pragma unroll
+                for (int im = 0; im < 2; ++im)
+                    acc[in][im] = mfma32(fb[in], fa[im], acc[in][im]);              // D[n][m]
+        }
+    };
+
+    const int nk = (P.k + GBK - 1) / GBK;
+    stage_load(0);
+    stage_write(0);
+    __syncthreads();
+
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) stage_load((kt + 1) * GBK);
+        mac_tile(buf);
+        if (kt + 1 < nk) stage_write(buf ^ 1);
+        __syncthreads();
+    }
+
+    {                                      // acc += LA LB^T: the same loop on the low-rank operands (k % 64 == 0)
+        const GemmLRDesc& L = lr->p[tc.p];
+        const T* __restrict__ LA = reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a;
+        const T* __restrict__ LB = reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b;
+        auto lr_load = [&](int k0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = srow + 32 * i;
+                ra[i] = (m0 + r) < P.m ? *reinterpret_cast<const T8*>(LA + (int64_t)(m0 + r) * L.lda + k0 + scol) : zero8<T>();
+                rb[i] = (n0 + r) < P.n ? *reinterpret_cast<const T8*>(LB + (int64_t)(n0 + r) * L.ldb + k0 + scol) : zero8<T>();
+            }
+        };
+        const int nl = L.k / GBK;
+        if (nl > 0) {
+            lr_load(0);
+            stage_write(0);
+            __syncthreads();
+        }
+        for (int kt = 0; kt < nl; ++kt) {
+            const int buf = kt & 1;
+            if (kt + 1 < nl) lr_load((kt + 1) * GBK);
+            mac_tile(buf);
+            if (kt + 1 < nl) stage_write(buf ^ 1);
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue: lane (m = l31, hi) holds n = 8*g + 4*hi + {0..3} for g = r>>2 -------------
+    mfma_fence(acc);
+    const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
+#pragma unroll
+    for (int im = 0; im < 2; ++im) {
+        const int m = m0 + wm + im * 32 + l31;
+        if (m >= P.m) continue;
+#pragma unroll
+        for (int in = 0; in < 2; ++in) {
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const int n = n0 + wn + in * 32 + gq * 8 + hi * 4;
+                if (n >= P.n) continue;
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[in][im][gq * 4 + e];
+                if (P.ln_stats) ln_fix4(P, P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats, m, n, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] *= P.scale;
+                if (bias) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (n + e < P.n) v[e] += (float)bias[n + e];
+                }
+                if (P.residual) {                       // added after the first rounding, like the reference's separate add
+                    const T* R = reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c + (int64_t)m * P.ldc + n;
+                    const f32x4 r0 = up4<T>(cvt4<T>(v));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (n + e < P.n) ? r0[e] + (float)R[e] : 0.f;
+                }
+                // columns [n, round_up(n, 4)) are written with zeros (aid_hip.h): the guarded loads leave their accumulators 0, but the
+                // folded LayerNorm's fix-up (or a negative scale) does not keep them there
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n + e >= P.n) v[e] = 0.f;
+                *reinterpret_cast<T4*>(C + (int64_t)m * P.ldc + n) = cvt4<T>(v);
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel_lr(const GemmGroup g, const GemmLR lr) {
+    gemm_edge_tile_lr<T>(g, &lr);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Fast epilogue (tile columns inside the matrix, 16-byte aligned rows / pointers): straight-line code.
@@ -439,6 +601,22 @@ struct Engine {
             const int row = RPI * (IPB * wave + j) + lane / CPR;
             const int c = (lane % CPR) ^ swz(row);
             bsrc[j] = B + (int64_t)min(n0 + row, P.n - 1) * P.ldb + c * 8;
+        }
+    }
+
+    // the same for the low-rank segment (GemmLR): A = LA [m, lr k] (row stride lda), B = LB [n, lr k] (row stride ldb)
+    __device__ __forceinline__ void set_tile_lr(int m, int n, int lda, int ldb, const T* A, const T* B, int m0, int n0) {
+#pragma unroll
+        for (int j = 0; j < IPA; ++j) {
+            const int row = RPI * (IPA * wave + j) + lane / CPR;
+            const int c = (lane % CPR) ^ swz(row);
+            asrc[j] = A + (int64_t)min(m0 + row, m - 1) * lda + c * 8;
+        }
+#pragma unroll
+        for (int j = 0; j < IPB; ++j) {
+            const int row = RPI * (IPB * wave + j) + lane / CPR;
+            const int c = (lane % CPR) ^ swz(row);
+            bsrc[j] = B + (int64_t)min(n0 + row, n - 1) * ldb + c * 8;
         }
     }
 
@@ -1435,6 +1613,31 @@ __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const Ge
                      P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
 }
 
+// The same with the low-rank segment: mac() ends with no VMEM operation outstanding and the ring released, so the segment is a second
+// set_tile + mac over the LA / LB operands into the same accumulators.
+template <typename T, int BM, int BN, int BK, int NS, int WM, int WN>
+__global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel_lr(const GemmGroup g, const GemmLR lr) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const TileCoord tc = locate_tile<BM, BN>(g, blockIdx.x, gridDim.x);
+    const GemmDesc& P = g.p[tc.p];
+    const T* A = reinterpret_cast<const T*>(P.a) + (int64_t)tc.batch * P.stride_a;
+    const T* B = reinterpret_cast<const T*>(P.b) + (int64_t)tc.batch * P.stride_b;
+    T* C = reinterpret_cast<T*>(P.c) + (int64_t)tc.batch * P.stride_c;
+    Engine<T, BM, BN, BK, NS, WM, WN> e;
+    e.init(smem_raw);
+    e.set_tile(P, A, B, tc.m0, tc.n0);
+    e.zero_acc();
+    e.mac(0, P.k / BK);
+    const GemmLRDesc& L = lr.p[tc.p];
+    if (L.k > 0) {
+        e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
+                      reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
+        e.mac(0, L.k / BK);
+    }
+    e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
+                     P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side: plan_gemm picks the engine of a group and launches nothing; launch_plan runs the plan.
 // ------------------------------------------------------------------------------------------------
@@ -1477,6 +1680,31 @@ static hipError_t launch_pipe(GemmGroup& g, hipStream_t stream) {
     static PerDevice<int> attr_set;
     return launch_with_smem(aid_gemm_nt_pipe_kernel<T, 128, 128, 64, NS, 2, 4>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g,
                             128, 128, stream, 512);
+}
+
+// the `_lr` kernels take the GemmLR next to the group
+template <typename K>
+static hipError_t launch_lr(K kernel, size_t smem, PerDevice<int>& attr_set, GemmGroup& g, const GemmLR& lr, int bm, int bn,
+                            hipStream_t stream, int threads) {
+    const int tiles = fill_tile_start(g, bm, bn);
+    if (tiles <= 0) return hipSuccess;
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(kernel), smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(threads), smem, stream, g, lr);
+    return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_edge_lr(GemmGroup& g, const GemmLR& lr, hipStream_t stream) {
+    static PerDevice<int> attr_set;
+    return launch_lr(aid_gemm_nt_kernel_lr<T>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), attr_set, g, lr, GBM, GBN, stream, GTHREADS);
+}
+
+template <typename T, int NS>
+static hipError_t launch_pipe_lr(GemmGroup& g, const GemmLR& lr, hipStream_t stream) {
+    static PerDevice<int> attr_set;
+    return launch_lr(aid_gemm_nt_pipe_kernel_lr<T, 128, 128, 64, NS, 2, 4>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g, lr,
+                     128, 128, stream, 512);
 }
 
 template <typename T, int PPV>
@@ -1565,11 +1793,14 @@ struct GemmPlan {
     const char* variant;                    // aid_last_gemm_variant()
     const char* symbol;                     // kernel symbol, for the profile entries
     bool writes_trans;                      // the engine writes the C of a trans_rows problem itself
+    bool lr;                                // the group carries low-rank segments: the `_lr` kernel of the engine runs
 };
 
-static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide& sd, int ncu, int n_big = 0, int n_small = 0) {
+static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide& sd, int ncu, int n_big = 0, int n_small = 0,
+                          bool lr = false) {
     GemmPlan pl;
     pl.engine = engine;
+    pl.lr = lr;
     pl.g = g;
     pl.sd = sd;
     pl.n_big = n_big;
@@ -1597,6 +1828,7 @@ static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide&
             pl.symbol = "aid_gemm_rs_kernel";
             break;
     }
+    if (lr) pl.symbol = engine == GemmEngine::Edge ? "aid_gemm_nt_kernel_lr" : "aid_gemm_nt_pipe_kernel_lr";
     // transposed C: the row-stationary engine and the 288-row tiles write it; side tiles run on the 128 x 128 engine, which does not
     pl.writes_trans = engine == GemmEngine::Rowstat || engine == GemmEngine::Pp288;
     for (int i = 0; i < sd.n; ++i) pl.writes_trans = pl.writes_trans && !sd.p[i].trans_rows;
@@ -1613,12 +1845,14 @@ static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide&
 // (the text-context projections of cross-attention: their tiles are mostly padding at 256 x 256).
 // Two CU counts: `device_cu` is the device's, `ncu` (device_cu after the CU_SHARE hint) the one the tile engines plan with.  The
 // row-stationary size rule and the GEMM_LS default look at the device's.
-static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share) {
+// A group with low-rank segments (lr) runs on the engines that carry them: the edge kernel for ragged k, the lock-step engine (either
+// ring) otherwise.  The ping-pong engines and the row-stationary one are planned around (DESIGN.md "LoRA").
+static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool lr = false) {
     GemmSide sd;
     memset(&sd, 0, sizeof(sd));
     bool k64 = true;
     for (int i = 0; i < g.n_problems; ++i) k64 = k64 && (g.p[i].k % 64 == 0);
-    if (!k64) return make_plan(GemmEngine::Edge, g, sd, device_cu);
+    if (!k64) return make_plan(GemmEngine::Edge, g, sd, device_cu, 0, 0, lr);
     // development knob (tools/gemm_shapes.py): AID_GEMM_VARIANT=7 / 31 forces the lock-step / ping-pong engine
     const int force = tune(TUNE_GEMM_VARIANT);
     // CU_SHARE = n: n launch streams share the device (the two passes of a step on two streams): a launch can count on 1 / n of the
@@ -1631,8 +1865,8 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share) {
     // (the size rule looks at the DEVICE's CU count, not at the share the caller's hint leaves: the engine choice between this engine
     //  and the tile engines — whose summation orders differ — must not depend on cu_share; only the split of the slice range does)
     const int rs = tune(TUNE_GEMM_RS);
-    if (rs != 0 && force < 0 && gemm_rs_supported(g, device_cu, rs == 1)) return make_plan(GemmEngine::Rowstat, g, sd, ncu);
-    if (g.interleave && g.n_problems > 1 && force != 7) {
+    if (!lr && rs != 0 && force < 0 && gemm_rs_supported(g, device_cu, rs == 1)) return make_plan(GemmEngine::Rowstat, g, sd, ncu);
+    if (!lr && g.interleave && g.n_problems > 1 && force != 7) {
         // K loops differ: if a few short problems (<= 15 % of the flops) sit next to main problems of ONE K that the
         // ping-pong engine would win, run the short ones as side tiles of the ping-pong launch
         double fl[AID_GEMM_MAX_PROBLEMS], tot = 0, best = -1;
@@ -1692,7 +1926,7 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share) {
         pp = cost_pp < 0.95 * cost_ls;
         if (force == 31) pp = true;
     }
-    if (force == 7) pp = false;
+    if (force == 7 || lr) pp = false;
     if (pp && prefer_ppx(g, ncu, sp.rounds)) return make_plan(GemmEngine::Pp288, g, sd, ncu);
     if (pp) return make_plan(sp.n_small ? GemmEngine::Pp256Tail : GemmEngine::Pp256, g, sd, ncu, sp.n_big, sp.n_small);
     // 8 waves, 64 x 32 wave tiles.  The ring: a K tile's loads are in flight for ~0.75 us whatever the launch (HBM / L2 latency), so a
@@ -1709,11 +1943,19 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share) {
         for (int i = 0; i < g.n_problems; ++i) nk_min = g.p[i].k / 64 < nk_min ? g.p[i].k / 64 : nk_min;
         ls = (t128 >= 64 && t128 <= device_cu && nk_min >= 16) ? 1 : 0;
     }
-    return make_plan(ls == 1 ? GemmEngine::Lockstep4 : GemmEngine::Lockstep, g, sd, ncu);     // Lockstep: 2 workgroups / CU
+    return make_plan(ls == 1 ? GemmEngine::Lockstep4 : GemmEngine::Lockstep, g, sd, ncu, 0, 0, lr);     // Lockstep: 2 workgroups / CU
 }
 
 template <typename T>
-static hipError_t launch_plan(GemmPlan& pl, hipStream_t stream) {
+static hipError_t launch_plan(GemmPlan& pl, hipStream_t stream, const GemmLR* lr) {
+    if (pl.lr) {
+        switch (pl.engine) {
+            case GemmEngine::Edge:      return launch_edge_lr<T>(pl.g, *lr, stream);
+            case GemmEngine::Lockstep:  return launch_pipe_lr<T, 2>(pl.g, *lr, stream);
+            case GemmEngine::Lockstep4: return launch_pipe_lr<T, 4>(pl.g, *lr, stream);
+            default:                    return hipErrorInvalidValue;     // plan_gemm never plans another engine for it
+        }
+    }
     switch (pl.engine) {
         case GemmEngine::Edge:      return launch_edge<T>(pl.g, stream);
         case GemmEngine::Lockstep:  return launch_pipe<T, 2>(pl.g, stream);
@@ -1735,10 +1977,17 @@ static bool has_trans(const GemmGroup& g) {
         if (g.p[i].trans_rows) return true;
     return false;
 }
-static void untranspose(GemmGroup& g) {
+static void untranspose(GemmGroup& g, GemmLR* lr) {
     for (int i = 0; i < g.n_problems; ++i) {
         GemmDesc& d = g.p[i];
         if (!d.trans_rows) continue;
+        if (lr && lr->p[i].k > 0) {                              // LA = U [frames * rows, r] -> LB[f]; LB = B_v [n, r] -> shared LA
+            GemmLRDesc& L = lr->p[i];
+            const GemmLRDesc o = L;
+            L.a = o.b; L.b = o.a;
+            L.lda = o.ldb; L.ldb = o.lda;
+            L.stride_a = 0; L.stride_b = (int64_t)d.trans_rows * o.lda;
+        }
         const int rows = d.trans_rows, frames = d.m / rows;
         GemmDesc o = d;
         o.a = d.b; o.b = d.a;
@@ -1752,7 +2001,11 @@ static void untranspose(GemmGroup& g) {
     }
 }
 
-hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant, const char** symbol, int cu_share) {
+hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant, const char** symbol, int cu_share,
+                             GemmLR* lr) {
+    bool has_lr = false;
+    for (int i = 0; lr && i < g.n_problems; ++i) has_lr = has_lr || lr->p[i].k > 0;
+    if (!has_lr) lr = nullptr;
     // Longest K loop first: blocks are dispatched in grid order, so the tiles that take longest (the K = 2048
     // text-context projections of a cross-attention layer next to its K = 1280 query projection) start first
     // and finish under the rest instead of forming the tail of the launch (measured: 107 -> 7x us).
@@ -1764,17 +2017,22 @@ hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const 
             const GemmDesc t = g.p[j];
             g.p[j] = g.p[j - 1];
             g.p[j - 1] = t;
+            if (lr) {
+                const GemmLRDesc u = lr->p[j];
+                lr->p[j] = lr->p[j - 1];
+                lr->p[j - 1] = u;
+            }
         }
     const int device_cu = num_cu();
     if (device_cu <= 0) return hipErrorInvalidDevice;
-    GemmPlan pl = plan_gemm(g, device_cu, cu_share);
+    GemmPlan pl = plan_gemm(g, device_cu, cu_share, lr != nullptr);
     if (has_trans(g) && !pl.writes_trans) {
-        untranspose(g);
-        pl = plan_gemm(g, device_cu, cu_share);
+        untranspose(g, lr);
+        pl = plan_gemm(g, device_cu, cu_share, lr != nullptr);
     }
     if (variant) *variant = pl.variant;
     if (symbol) *symbol = pl.symbol;
-    return dtype == AID_DTYPE_F16 ? launch_plan<f16>(pl, stream) : launch_plan<bf16>(pl, stream);
+    return dtype == AID_DTYPE_F16 ? launch_plan<f16>(pl, stream, lr) : launch_plan<bf16>(pl, stream, lr);
 }
 
 }  // namespace aid

@@ -34,6 +34,19 @@ struct GemmGroup {                        // passed by value as the kernel argum
     int32_t  interleave;                              // 1: every XCD gets a chunk of each problem (unequal K loops)
 };
 
+// Low-rank second K segment of a problem (AidGemmProblem.lr_*): acc += LA[m0.., 0:k] LB[n0.., 0:k]^T after the main K loop, before
+// the epilogue.  A kernel argument of its own, next to the GemmGroup, of the `_lr` kernel instantiations only: the kernels without it
+// keep their arguments and code.  Entry i belongs to GemmGroup.p[i] (k = 0: none).
+struct GemmLRDesc {
+    const void* a;                                    // [m, k] (row stride lda), batch b at a + b * stride_a
+    const void* b;                                    // [n, k] (row stride ldb)
+    int32_t k, lda, ldb, reserved;
+    int64_t stride_a, stride_b;
+};
+struct GemmLR {
+    GemmLRDesc p[AID_GEMM_MAX_PROBLEMS];
+};
+
 // Side problems of a ping-pong launch: the few short problems of a group whose K loop differs from the main ones (the
 // K = 2048 text-context projections next to the K = 1280 query projection of a cross-attention layer).  They run as
 // 128 x 128 lock-step tiles in the FIRST blocks of the same launch, so the main problems keep the big-tile engine.
@@ -73,15 +86,16 @@ int tune(int id);
 
 // picks the engine and launches it; `variant` / `symbol` receive the engine's name and its kernel symbol
 // cu_share > 1: the caller runs that many launch streams side by side (AidGemmProblem.cu_share); 0 / 1: the process-wide CU_SHARE knob decides
+// lr (optional): low-rank segments of the problems; a group with any lr->p[i].k > 0 runs on an engine that carries them (edge or lock-step)
 hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant = nullptr, const char** symbol = nullptr,
-                             int cu_share = 0);
+                             int cu_share = 0, GemmLR* lr = nullptr);
 
 // row-stationary engine (aid_gemm_rs.hip): K = 320 / 640, one shared tall activation; `ncu` = CUs the launch may count on
 bool       gemm_rs_supported(const GemmGroup& g, int ncu, bool ignore_size);
 hipError_t gemm_rs_launch(const GemmGroup& g, int dtype, int ncu, hipStream_t stream);
 
 // float32 storage path (aid_f32.hip)
-hipError_t gemm_f32_launch(GemmGroup& g, hipStream_t stream);
+hipError_t gemm_f32_launch(GemmGroup& g, hipStream_t stream, const GemmLR* lr = nullptr);
 hipError_t attn_f32_launch(const AidAttnArgs& a, hipStream_t stream);
 hipError_t lerp_kv_f32_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                               int end, int64_t k_fs, int64_t vt_fs, hipStream_t stream);

@@ -269,6 +269,14 @@ def gemm_nt(problems: Sequence[dict]) -> None:
                     raise TypeError("ln_stats / ln_colsum / ln_shift are contiguous float32 tensors")
             q.ln_stats, q.ln_colsum, q.ln_shift = p["ln_stats"].data_ptr(), p["ln_colsum"].data_ptr(), p["ln_shift"].data_ptr()
             q.ln_side, q.stride_stats = int(p["ln_side"]), int(p.get("stride_stats", 0))
+        lr = p.get("lr")
+        if lr is not None:      # low-rank second K segment: dict(a=LA [m, k], b=LB [n, k], k=, lda=, ldb=[, stride_a=, stride_b=])
+            _require_gpu(lr["a"], lr["b"])
+            if _dtype_code(lr["a"]) != dt or _dtype_code(lr["b"]) != dt:
+                raise TypeError("the low-rank operands must have the GEMM's dtype")
+            q.lr_a, q.lr_b = lr["a"].data_ptr(), lr["b"].data_ptr()
+            q.lr_k, q.lr_lda, q.lr_ldb = int(lr["k"]), int(lr["lda"]), int(lr["ldb"])
+            q.lr_stride_a, q.lr_stride_b = int(lr.get("stride_a", 0)), int(lr.get("stride_b", 0))
     with _on(problems[0]["a"].device):
         _lib.check(lib.aid_gemm_nt(arr, n, dt, _stream()), "aid_gemm_nt")
 
@@ -340,21 +348,39 @@ def ln_fold(w: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch
     return wf, cs, sh
 
 
-def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: int = 0,
+               lora_k: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               lora_v: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """k = e @ wk.T  [F, L, C]  and  V^T = wv @ e^T  [F, C, Lp]  (Lp = L rounded up to 8) in one launch.
     ``extra_rows``: allocate that many more (uninitialised) frame rows behind the F projected ones — room for the
-    end-point frames' keys / values a rank receives from their owners (dist.EndpointExchange)."""
+    end-point frames' keys / values a rank receives from their owners (dist.EndpointExchange).
+    ``lora_k`` / ``lora_v`` = (A_pack, B_pack) (lora.pack): the adapters' terms are added in the same accumulators; e is projected
+    down once, U = e [A_k; A_v]^T, in one launch before."""
     f, l, cc = e.shape
     c = wk.shape[0]
     lp = (l + 7) // 8 * 8
     k = torch.empty(f + extra_rows, l, c, dtype=e.dtype, device=e.device)
     vt = torch.empty(f + extra_rows, c, lp, dtype=e.dtype, device=e.device)
+    u = None
+    rk = lora_k[0].shape[0] if lora_k is not None else 0
+    rv = lora_v[0].shape[0] if lora_v is not None else 0
+    if rk + rv:
+        down = torch.cat([p[0] for p in (lora_k, lora_v) if p is not None], 0) if rk and rv else (lora_k or lora_v)[0]
+        u = torch.empty(f * l, rk + rv, dtype=e.dtype, device=e.device)
+        gemm_nt([dict(a=e, b=down, c=u, m=f * l, n=rk + rv, k=cc, lda=cc, ldb=cc, ldc=rk + rv)])
     if l % 8 == 0:          # flat value projection, transposed epilogue (tile count of the key projection: whole CU rounds)
         pv = dict(a=e, b=wv, c=vt, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=lp, stride_c=c * lp, trans_rows=l)
+        if rv:
+            pv["lr"] = dict(a=u[:, rk:], b=lora_v[1], k=rv, lda=rk + rv, ldb=rv)
     else:                   # V^T[f] = Wv E_f^T, one batch entry per frame.  Pad columns l .. round_up(l, 4) of V^T are written with
         #                     zeros (aid_hip.h); round_up(l, 4) .. lp are not written, and the attention kernels do not read their values
         pv = dict(a=wv, b=e, c=vt, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=lp, batch=f, stride_a=0, stride_b=l * cc, stride_c=c * lp)
-    gemm_nt([dict(a=e, b=wk, c=k, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c), pv])
+        if rv:
+            pv["lr"] = dict(a=lora_v[1], b=u[:, rk:], k=rv, lda=rv, ldb=rk + rv, stride_b=l * (rk + rv))
+    pk = dict(a=e, b=wk, c=k, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c)
+    if rk:
+        pk["lr"] = dict(a=u, b=lora_k[1], k=rk, lda=rk + rv, ldb=rk)
+    gemm_nt([pk, pv])
     return k, vt
 
 
@@ -475,7 +501,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   residual: Optional[torch.Tensor] = None, seg_executed: int = 0,
                   ip: Optional[dict] = None, ln_folded: Optional[tuple] = None,
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                  attn_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  attn_bias: Optional[torch.Tensor] = None, lora=None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -489,7 +515,10 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``kv_cached`` = (k, vt) from ``project_kv(ctx, wk, wv)``: the step-invariant keys / values of a cross-attention layer,
     projected once by the caller; the call then projects the queries only.
     ``attn_bias``: additive score bias of the (text) attention — diffusers' prepared attention_mask (AidProcessorArgs.attn_bias,
-    ``score_bias_layout``); the library refuses it together with ``fused`` or ``ip`` (the reference fails there, aid_hip.h)."""
+    ``score_bias_layout``); the library refuses it together with ``fused`` or ``ip`` (the reference fails there, aid_hip.h).
+    ``lora``: unmerged LoRA adapters of the four projections (``lora.LoraArgs``, AidProcessorArgs.lora_*): each projection with a
+    rank computes  in W^T + round(in A_pack^T) B_pack^T  in its GEMM accumulator; refused with ``ln_folded`` and, on k / v, with
+    ``kv_cached`` (the cached keys must already hold the adapter term)."""
     lib = _lib.load()
     ipt = ip or {}
     dev = _require_gpu(x, ctx, wq, wk, wv, wo, bo, coef, ctx_map, out, residual, attn_bias, *(ln[:2] if ln else ()),
@@ -576,6 +605,15 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     if attn_bias is not None:
         a.attn_bias = attn_bias.data_ptr()
         a.attn_bias_fs, a.attn_bias_hs, a.attn_bias_rs = score_bias_layout(attn_bias, n, heads, s, a.l, x.dtype)
+    if lora is not None:
+        for t_ in (lora.down_x, lora.down_ctx, lora.down_o, *lora.up):
+            if t_ is not None:
+                _require_gpu(t_)
+                if t_.dtype != x.dtype or not t_.is_contiguous():
+                    raise ValueError("LoRA packs must be contiguous tensors of the activation dtype")
+        a.lora_down_x, a.lora_down_ctx, a.lora_down_o = _ptr(lora.down_x), _ptr(lora.down_ctx), _ptr(lora.down_o)
+        a.lora_up_q, a.lora_up_k, a.lora_up_v, a.lora_up_o = (_ptr(t_) for t_ in lora.up)
+        a.lora_r_q, a.lora_r_k, a.lora_r_v, a.lora_r_o = lora.ranks
     a.cu_share = current_cu_share()
     nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):

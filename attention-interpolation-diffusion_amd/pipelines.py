@@ -167,7 +167,8 @@ class _PassGraphs:
     ``activate_aid(it)`` rewrites the coefficient buffers in place, so a replay reads the live schedule.
 
     What a replay FREEZES: every Python-side decision of the first call of a pass kind — the frame -> context map
-    (``ctx_index``), ``plain_tail``, the IP-Adapter scales, which processor object sits on which layer.  A
+    (``ctx_index``), ``plain_tail``, the IP-Adapter scales, which processor object sits on which layer, and the unmerged LoRA
+    adapters: their active set, their scalings (``cross_attention_kwargs["scale"]`` included) and the packed factors (lora.py).  A
     ``callback_on_step_end`` that swaps processors or embeddings between steps has no effect on replayed passes: run such loops
     with ``use_graphs=False``.  Each pass kind also holds a private pool with one UNet pass of activations.
 
@@ -258,11 +259,12 @@ class InterpolationStableDiffusionPipeline:
     @classmethod
     def from_pipe(cls, pipe):
         """Take ``unet / scheduler / vae / encode_prompt`` from a loaded diffusers (SD or SDXL) pipeline."""
-        def enc(prompt, negative_prompt=None):
-            out = pipe.encode_prompt(prompt, pipe._execution_device, 1, True, negative_prompt=negative_prompt) \
+        def enc(prompt, negative_prompt=None, lora_scale=None):
+            out = pipe.encode_prompt(prompt, pipe._execution_device, 1, True, negative_prompt=negative_prompt,
+                                     lora_scale=lora_scale) \
                 if not cls.is_xl else pipe.encode_prompt(prompt=prompt, device=pipe._execution_device,
                                                          num_images_per_prompt=1, do_classifier_free_guidance=True,
-                                                         negative_prompt=negative_prompt)
+                                                         negative_prompt=negative_prompt, lora_scale=lora_scale)
             return out
         sf = getattr(getattr(pipe.vae, "config", None), "scaling_factor", 0.18215)
         enc_img = None
@@ -275,7 +277,37 @@ class InterpolationStableDiffusionPipeline:
                 return neg, pos
         obj = cls(pipe.unet, pipe.scheduler, pipe.vae, encode_prompt=enc, encode_image=enc_img, vae_scaling_factor=sf)
         obj._load_ip_adapter = getattr(pipe, "load_ip_adapter", None)      # diffusers' loader: load_aid_ip_adapter(path, ...) uses it
+        obj._pipe = pipe                                                  # its LoRA loader methods (load_lora_weights & co.) below
         return obj
+
+    # -- LoRA (diffusers' StableDiffusionLoraLoaderMixin of the wrapped pipeline, pipeline_interpolated_sd.py:283-299) ----------------
+    # Each method changes adapter weights or their state in place; the caches derived from weights are dropped after it, like
+    # _load_ip_adapter does.  Unmerged adapters run inside the projection GEMMs (lora.py); fuse_lora() folds them into the weights.
+    def _lora_call(self, name: str, *args, **kwargs):
+        fn = getattr(getattr(self, "_pipe", None), name, None)
+        if fn is None:
+            raise RuntimeError(f"{name} is diffusers' LoRA loader: wrap a diffusers pipeline with from_pipe")
+        out = fn(*args, **kwargs)
+        P.clear_weight_caches()
+        return out
+
+    def load_lora_weights(self, *args, **kwargs):
+        return self._lora_call("load_lora_weights", *args, **kwargs)
+
+    def set_adapters(self, *args, **kwargs):
+        return self._lora_call("set_adapters", *args, **kwargs)
+
+    def fuse_lora(self, *args, **kwargs):
+        return self._lora_call("fuse_lora", *args, **kwargs)
+
+    def unfuse_lora(self, *args, **kwargs):
+        return self._lora_call("unfuse_lora", *args, **kwargs)
+
+    def enable_lora(self, *args, **kwargs):
+        return self._lora_call("enable_lora", *args, **kwargs)
+
+    def disable_lora(self, *args, **kwargs):
+        return self._lora_call("disable_lora", *args, **kwargs)
 
     # -- the reference's AID methods ----------------------------------------------------------------
     def load_aid(self, t: Optional[float] = 0.5, is_fused: bool = True, atype: str = "fused_outer", **kw):
@@ -313,12 +345,14 @@ class InterpolationStableDiffusionPipeline:
         return self._guidance_scale > 1
 
     # -- helpers ---------------------------------------------------------------------------------------
-    def _embed(self, prompt, negative_prompt, given):
+    def _embed(self, prompt, negative_prompt, given, lora_scale=None):
         if given is not None:
             return tuple(given)
         if prompt is None or self._encode_prompt is None:
             raise ValueError("pass a prompt and an `encode_prompt` component, or the embeddings themselves "
                              "(embeds_start / embeds_end / embeds_guide)")
+        if lora_scale is not None:          # cross_attention_kwargs["scale"] -> encode_prompt(lora_scale=) (pipeline_interpolated_sd.py:1647-1686)
+            return tuple(self._encode_prompt(prompt, negative_prompt, lora_scale=lora_scale))
         return tuple(self._encode_prompt(prompt, negative_prompt))
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
@@ -333,7 +367,10 @@ class InterpolationStableDiffusionPipeline:
     def _added_cond(self, pooled, n: int, image_embeds=None) -> Optional[Dict[str, Any]]:
         return None if image_embeds is None else {"image_embeds": image_embeds}
 
-    def _unet(self, latents, t, ctx, added):
+    def _unet(self, latents, t, ctx, added, cross_attention_kwargs=None):
+        if cross_attention_kwargs is not None:      # diffusers' UNet applies its "scale" to the LoRA layers for the call
+            return self.unet(latents, t, encoder_hidden_states=ctx, added_cond_kwargs=added,
+                             cross_attention_kwargs=cross_attention_kwargs, return_dict=False)[0]
         return self.unet(latents, t, encoder_hidden_states=ctx, added_cond_kwargs=added, return_dict=False)[0]
 
     def _decode(self, latents, output_type: str):
@@ -380,11 +417,13 @@ class InterpolationStableDiffusionPipeline:
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
         self._guidance_scale = gs
         dev, dtype = self._unet_device_dtype()
-        cond_s, unc_s = self._split(self._embed(prompt_start, negative_prompt, embeds_start))
-        cond_e, unc_e = self._split(self._embed(prompt_end, negative_prompt, embeds_end))
+        cak = cross_attention_kwargs
+        ls = cak.get("scale", None) if cak is not None else None
+        cond_s, unc_s = self._split(self._embed(prompt_start, negative_prompt, embeds_start, ls))
+        cond_e, unc_e = self._split(self._embed(prompt_end, negative_prompt, embeds_end, ls))
         guide = None
         if guide_prompt is not None or embeds_guide is not None:
-            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide))
+            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide, ls))
         h = height or self._latent_hw()[0] * 8
         w = width or self._latent_hw()[1] * 8
         nc = getattr(self.unet, "in_channels", 4)
@@ -406,10 +445,10 @@ class InterpolationStableDiffusionPipeline:
         added_u = self._added_cond(None if pooled is None else pooled[1], 3, None if img is None else img[1])
 
         def cond_pass(x, t):
-            return self._unet(x, t, cond, added_c)
+            return self._unet(x, t, cond, added_c, cak)
 
         def uncond_pass(x, t):
-            return self._unet(x, t, unc, added_u)
+            return self._unet(x, t, unc, added_u, cak)
 
         for i, t in enumerate(self.scheduler.timesteps):
             x = self.scheduler.scale_model_input(lat, t)
@@ -438,24 +477,27 @@ class InterpolationStableDiffusionPipeline:
                     beta: Optional[float] = None, guidance_scale: Optional[float] = None,
                     # build-specific
                     embeds_start=None, embeds_end=None, embeds_guide=None, batched_cfg: bool = True,
-                    output_type: str = "np", coef: Optional[Sequence[float]] = None, use_graphs: Optional[bool] = None):
+                    output_type: str = "np", coef: Optional[Sequence[float]] = None, use_graphs: Optional[bool] = None,
+                    cross_attention_kwargs: Optional[Dict[str, Any]] = None):
         """gradio_src/pipeline_interpolated_stable_diffusion.py:163-304 with the root pipelines' warm-up count
         (``i < int(T * warmup_ratio)`` with 0-based ``i``).  ``late`` must be "self" (plain
         attention) or one of the AID modes.  ``batched_cfg``: the two passes of a step run as one UNet call.
         ``coef`` (build-specific, ``[0, t_1, ..., 1]``): render the frames at THESE coefficients the way
         ``interpolate_single(t_k)`` would — latents slerp'd and embeddings lerp'd at ``t_k``, attention coefficient
         ``t_k`` — in one N-frame run (the Beta-prior exploration fills several gaps per run with it, prior.py).
-        ``use_graphs`` as in ``interpolate_single``.  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
+        ``use_graphs`` and ``cross_attention_kwargs`` as in ``interpolate_single``.  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
         back when the run ends (the run works with its own N-frame processors)."""
         if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
             raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
         dev, dtype = self._unet_device_dtype()
-        cond_s, unc_s = self._split(self._embed(prompt_start, negative_prompt, embeds_start))
-        cond_e, unc_e = self._split(self._embed(prompt_end, negative_prompt, embeds_end))
+        cak = cross_attention_kwargs
+        ls = cak.get("scale", None) if cak is not None else None
+        cond_s, unc_s = self._split(self._embed(prompt_start, negative_prompt, embeds_start, ls))
+        cond_e, unc_e = self._split(self._embed(prompt_end, negative_prompt, embeds_end, ls))
         guide = None
         if guide_prompt is not None or embeds_guide is not None:
-            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide))
+            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide, ls))
         batch = prepare_sequence(latent_start.to(dev, dtype), latent_end.to(dev, dtype), cond_s[0], cond_e[0], unc_s[0],
                                  unc_e[0], size=size, guide_emb=None if guide is None else guide[0][0],
                                  uncond_guide=None if guide is None else guide[1][0],
@@ -494,13 +536,13 @@ class InterpolationStableDiffusionPipeline:
                 added_u = self._added_cond(None if pooled is None else pooled[1], size)
 
             def both_pass(x, t):
-                return self._unet(torch.cat([x, x]), t, ctx_both, added_both)
+                return self._unet(torch.cat([x, x]), t, ctx_both, added_both, cak)
 
             def cond_pass(x, t):
-                return self._unet(x, t, cond, added_c)
+                return self._unet(x, t, cond, added_c, cak)
 
             def uncond_pass(x, t):
-                return self._unet(x, t, unc, added_u)
+                return self._unet(x, t, unc, added_u, cak)
 
             for i, t in enumerate(self.scheduler.timesteps):
                 x = self.scheduler.scale_model_input(lat, t)

@@ -29,7 +29,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from . import ops
+from . import lora, ops
 from .interp import generate_beta_tensor
 
 
@@ -279,6 +279,8 @@ def _ln_folded(attn, norm, cross: bool):
     """(wq', wk', wv', const [6, C]) for ops.processor_fwd(ln_folded=...), or None where folding does not apply."""
     if os.environ.get("AID_LN_FOLD", "1") == "0":
         return None
+    if lora.any_lora(attn) and any(lora.active(m) for m in lora.projections(attn)[:3]):
+        return None                      # an adapter term on q / k / v must not be scaled by the fold's correction: LayerNorm(x) is written
     wq, wk, wv, _, _ = _weights(attn)
     c = wq.shape[1]
     if c % 64 or (not cross and (wk.shape[1] != c or wv.shape[1] != c)):
@@ -341,6 +343,7 @@ def clear_weight_caches() -> None:
     before the call still read the old derived tensors and must be re-captured."""
     _KV_CACHE.clear()
     _FOLD_CACHE.clear()
+    lora.clear()
     _CACHE_GEN[0] += 1
 
 
@@ -357,7 +360,9 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
     ks = (_vkey(ehs), _vkey(wk), _vkey(wv))
     if None in ks:
         return None
-    key = ks + (tuple(ehs.shape), ehs.dtype, tuple(idx) if idx is not None else None)
+    lk, lv = lora.kv_packs(attn, ctx.dtype, ctx.device)          # unmerged LoRA of to_k / to_v: part of the projection and of the key
+    key = ks + (tuple(ehs.shape), ehs.dtype, tuple(idx) if idx is not None else None,
+                None if lk is None else lk.key, None if lv is None else lv.key)
     try:
         per = _KV_CACHE.get(attn)
         if per is None:
@@ -368,8 +373,9 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
     hit = per.get(key)
     if hit is None:
         _CACHE_GEN[0] += 1
-        k, vt = ops.project_kv(ctx, wk, wv)
-        for old in [kk for kk in per if kk[0][0] == key[0][0] and kk[3:] == key[3:]]:
+        kw = {} if lk is None and lv is None else dict(lora_k=None if lk is None else lk[:2], lora_v=None if lv is None else lv[:2])
+        k, vt = ops.project_kv(ctx, wk, wv, **kw)
+        for old in [kk for kk in per if kk[0][0] == key[0][0] and kk[3:6] == key[3:6]]:
             per.pop(old, None)            # the same tensor at an older version (or with replaced weights)
 
         def _drop(_ref, per=per, key=key):
@@ -377,6 +383,13 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
         hit = (k, vt, weakref.ref(ehs, _drop))
         per[key] = hit
     return hit[0], hit[1]
+
+
+def _kv_and_lora(attn, ehs, ctx, idx, wk, wv, x):
+    """(kv_cached, lora) of a processor call: the cached text keys / values (they hold the k / v adapter terms already) and the
+    LoRA operands of the projections the call still runs."""
+    kv = _text_kv(attn, ehs, ctx, idx, wk, wv) if ctx is not None else None
+    return kv, lora.args(attn, x.dtype, x.device, ctx is not None, kv=kv is None)
 
 
 def _plain_sublayer_ok(attn, hidden_states) -> bool:
@@ -404,6 +417,8 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
     ctx_index = proc.ctx_index if ctx_index is None else ctx_index
     exchange = getattr(proc, "endpoint_exchange", None)
     if exchange is not None and mode != "plain":
+        if lora.any_lora(attn) and any(lora.active(m) for m in lora.projections(attn)):
+            raise NotImplementedError("unmerged LoRA adapters in the end-point exchange layout: fuse them (fuse_lora()) first")
         if bias is not None:
             raise NotImplementedError("the end-point exchange layout takes no attention_mask")
         if ln is not None or add_to is not None:
@@ -465,11 +480,12 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
     elif ctx is not None:
         ctx = ctx.contiguous()
     fused = proc.is_fused if mode != "plain" else False
+    kv, la = _kv_and_lora(attn, ehs, ctx, idx, wk, wv, x)
     y = ops.processor_fwd(x, ctx, wq, wk, wv, wo, bo, attn.heads, mode=mode, fused=fused, coef=coef,
                           begin=begin, end=end, ctx_map=ctx_map,
                           n_plain=proc.plain_tail if mode != "plain" else 0, ln=ln, residual=add_to, ln_folded=ln_folded,
                           seg_executed=ops.executed_segments(mode, fused, vals, x.shape[0], idx, begin, end),
-                          kv_cached=_text_kv(attn, ehs, ctx, idx, wk, wv) if ctx is not None else None, attn_bias=bias)
+                          kv_cached=kv, attn_bias=bias, lora=la)
     return _epilogue(attn, y, residual, shape4)
 
 
@@ -494,9 +510,10 @@ class HipAttnProcessor:
             ctx, ctx_map, idx = _shared_context(self._ctx_cache, ctx_index, ctx, x.shape[0])
         elif ctx is not None:
             ctx = ctx.contiguous()
+        kv, la = _kv_and_lora(attn, encoder_hidden_states, ctx, idx, wk, wv, x)
         return ops.processor_fwd(x, ctx, wq, wk, wv, wo, bo, attn.heads, mode="plain", ctx_map=ctx_map,
                                  ln=_ln_of(norm), residual=x, ln_folded=_ln_folded(attn, norm, ctx is not None),
-                                 kv_cached=_text_kv(attn, encoder_hidden_states, ctx, idx, wk, wv) if ctx is not None else None)
+                                 kv_cached=kv, lora=la)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  *args, ctx_index=None, **kwargs):
@@ -510,8 +527,9 @@ class HipAttnProcessor:
             ctx, ctx_map, idx = _shared_context(self._ctx_cache, ctx_index, ctx, x.shape[0])
         elif ctx is not None:
             ctx = ctx.contiguous()
+        kv, la = _kv_and_lora(attn, ehs, ctx, idx, wk, wv, x)
         y = ops.processor_fwd(x, ctx, wq, wk, wv, wo, bo, attn.heads, mode="plain", ctx_map=ctx_map,
-                              kv_cached=_text_kv(attn, ehs, ctx, idx, wk, wv) if ctx is not None else None, attn_bias=bias)
+                              kv_cached=kv, attn_bias=bias, lora=la)
         return _epilogue(attn, y, residual, shape4)
 
 
@@ -646,8 +664,10 @@ class HipIPAdapterAttnProcessor(nn.Module):
             tokens = rows.reshape(n, -1, rows.shape[-1])          # diffusers: ip_key.view(batch, -1, heads, head_dim)
             branch = dict(tokens=tokens, wk=self.to_k_ip[0].weight, wv=self.to_v_ip[0].weight, mode="plain",
                           scale=float(self.scale[0]))
+        _no_ip_lora(self)
         y = ops.processor_fwd(x, None if text is None else text.contiguous(), wq, wk, wv, wo, bo, attn.heads,
-                              mode="plain", ip=branch, attn_bias=bias)
+                              mode="plain", ip=branch, attn_bias=bias,
+                              lora=lora.args(attn, x.dtype, x.device, text is not None))
         return _epilogue(attn, y, residual, shape4)
 
 
@@ -709,10 +729,20 @@ class _IPBase(InterpolatedAttnProcessor):
         coef, vals = self._coef_state(x.device, x.dtype, x.shape[0])
         fused = self.is_fused if mode != "plain" else False
         branch = branch_of(ip, n, coef) if ip is not None else None
+        _no_ip_lora(self.ip_attn)
         y = ops.processor_fwd(x, None if text is None else text.contiguous(), wq, wk, wv, wo, bo, attn.heads,
                               mode=mode, fused=fused, coef=coef, begin=0, end=n - 1, ip=branch,
-                              seg_executed=ops.executed_segments(mode, fused, vals, n, None, 0, n - 1))
+                              seg_executed=ops.executed_segments(mode, fused, vals, n, None, 0, n - 1),
+                              lora=lora.args(attn, x.dtype, x.device, text is not None))
         return _epilogue(attn, y, residual, shape4)
+
+
+def _no_ip_lora(ip_attn) -> None:
+    """LoRA inside the IP-Adapter image projections is not computed: refuse it rather than drop it."""
+    for name in ("to_k_ip", "to_v_ip"):
+        for m in getattr(ip_attn, name, None) or ():
+            if lora.is_lora_layer(m) or getattr(m, "lora_layer", None) is not None:
+                raise NotImplementedError(f"a LoRA-wrapped {name}: the HIP path computes adapters on to_q / to_k / to_v / to_out only")
 
 
 def _zeros_map(cache, n: int, device) -> torch.Tensor:

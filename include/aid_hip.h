@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define AID_ABI_VERSION 8
+#define AID_ABI_VERSION 9
 
 /* element types of activations / weights (accumulation is always fp32) */
 #define AID_DTYPE_F16  0
@@ -114,6 +114,22 @@ typedef struct AidGemmProblem {
     /* a per-call hint (two host threads may pass different values); results never depend on it.  0 / 1: the whole device.          */
     int32_t      cu_share;
     int32_t      reserved0;
+    /* ABI v9 — low-rank second K segment (lr_k == 0: none): an unmerged LoRA adapter of the projection,                     */
+    /*     C = epilogue( scale * (A B^T + LA LB^T) + bias ... )                                                               */
+    /* LA = lr_a [m, lr_k] (row stride lr_lda), LB = lr_b [n, lr_k] (row stride lr_ldb), batch b at lr_a + b * lr_stride_a /   */
+    /* lr_b + b * lr_stride_b (0 = shared).  The term accumulates in fp32 with the main product, before every epilogue step.   */
+    /* Requirements: lr_k % 64 == 0, lr_k <= 512, lr_lda / lr_ldb % 8 == 0 and >= lr_k, lr_stride_* % 8 == 0, 16-byte bases;  */
+    /* not with ln_stats (AID_ERR_ARG: the folded LayerNorm's correction would scale the term too).  trans_rows, bias,        */
+    /* residual, batch > 1 and cu_share work as without it.  With trans_rows LA has the m = frames * rows layout of A (the     */
+    /* flat value projection: LA = U_v, LB = B_v); the batched V^T[f] = Wv E_f^T form takes LA = B_v (stride 0), LB = U_v[f]. */
+    const void*  lr_a;
+    const void*  lr_b;
+    int32_t      lr_k;
+    int32_t      lr_lda;
+    int32_t      lr_ldb;
+    int32_t      reserved1;
+    int64_t      lr_stride_a;
+    int64_t      lr_stride_b;
 } AidGemmProblem;
 
 int aid_gemm_nt(const AidGemmProblem* problems /* host */, int n_problems, int dtype, void* stream);
@@ -219,8 +235,8 @@ int aid_lerp_kv(const void* k, const void* vt, void* k2, void* vt2, const float*
  *   x   [n_frames, s, c]   hidden states          ctx [n_frames, l, cc] or NULL (self-attn: ctx = x)
  *   wq [c, c]  wk [c, cc]  wv [c, cc]  wo [c, c]  bo [c]      (torch Linear.weight layout [out, in])
  *   y   [n_frames, s, c]   = to_out( AID-attention( to_q(x), to_k(ctx), to_v(ctx) ) )
- * Launches: [1 LayerNorm or 1 row-statistics pass,] 1 grouped GEMM (q, k, V^T [, K_ip, V_ip^T]), [INNER: 1 streaming K/V lerp,] 1 attention
- * kernel [+ 1 for the image branch, accumulating], 1 GEMM (out-proj + bias [+ residual]).
+ * Launches: [1 LayerNorm or 1 row-statistics pass,] [LoRA: 1 down-projection GEMM,] 1 grouped GEMM (q, k, V^T [, K_ip, V_ip^T]), [INNER: 1 streaming K/V lerp,] 1 attention
+ * kernel [+ 1 for the image branch, accumulating], [LoRA on to_out: 1 down-projection GEMM,] 1 GEMM (out-proj + bias [+ residual]).
  * Optional block-level fusion: with ln_eps > 0 the call computes on LayerNorm(x) (the block's
  * norm1 / norm2; self-attention keys / values use the normalised x too, a cross-attention ctx is left alone), and
  * with `residual` it returns  residual + to_out(...)  — together  h + attn(norm(h))  in one call.
@@ -294,6 +310,28 @@ typedef struct AidProcessorArgs {
     const void*  attn_bias;
     int64_t      attn_bias_fs;
     int32_t      attn_bias_hs, attn_bias_rs;
+    /* ---- ABI v9: unmerged LoRA adapters of the four projections (all ranks 0: none).  Projection p in {q, k, v, o} with    */
+    /* lora_r_p > 0 computes  in W_p^T + U_p B_p^T  with  U_p = round(in A_p^T)  (`in` = its input: x, ctx or the attention    */
+    /* output o), where A_p [lora_r_p, in width] holds the adapters' lora_A weights stacked by rows, each multiplied by its   */
+    /* scaling, and B_p = lora_up_p [c, lora_r_p] their lora_B weights side by side (ranks zero-padded to a multiple of 64,   */
+    /* <= 512).  The down weights are stacked per input tensor, so that each input is read once:                             */
+    /*   lora_down_x   [r_q (+ r_k + r_v for self-attention), c]   rows A_q; A_k; A_v                                        */
+    /*   lora_down_ctx [r_k + r_v, cc]                             rows A_k; A_v   (cross-attention)                         */
+    /*   lora_down_o   [r_o, c]                                                                                             */
+    /* One extra GEMM launch projects x (and ctx) down, one o; U lives in the workspace (aid_processor_workspace_bytes grows  */
+    /* by it; unchanged with every rank 0).  Refused (AID_ERR_ARG): with ln_wq (the folded LayerNorm; pass ln_eps with        */
+    /* ln_wq = NULL instead), LoRA on k / v with k_cached (cached keys must already hold the adapter term).                   */
+    const void*  lora_down_x;
+    const void*  lora_down_ctx;
+    const void*  lora_down_o;
+    const void*  lora_up_q;
+    const void*  lora_up_k;
+    const void*  lora_up_v;
+    const void*  lora_up_o;
+    int32_t      lora_r_q;
+    int32_t      lora_r_k;
+    int32_t      lora_r_v;
+    int32_t      lora_r_o;
 } AidProcessorArgs;
 
 size_t aid_processor_workspace_bytes(const AidProcessorArgs* args /* host */);
@@ -304,7 +342,7 @@ int    aid_processor_fwd(const AidProcessorArgs* args /* host */, void* stream);
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
  * returns one entry per launch: elapsed milliseconds plus the ALGORITHMIC work of the launch
- * (flops: 2*m*n*k per GEMM problem, 4*s*l*c per (frame, key segment) of attention with the
+ * (flops: 2*m*n*(k + lr_k) per GEMM problem, 4*s*l*c per (frame, key segment) of attention with the
  * segment count of SURVEY.md §8d: plain 1, pure inner 1, fused inner 2, pure outer 2, fused
  * outer 3; bytes: operands read once + result written once).  Not for use inside stream capture.
  * ------------------------------------------------------------------------------------- */
