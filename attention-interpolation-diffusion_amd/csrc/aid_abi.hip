@@ -392,7 +392,8 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
             g_gemm_variant = "f32";
             ps.rename(has_lr ? "aid_gemm_f32_kernel_lr" : "aid_gemm_f32_kernel");
         } else {
-            // profile entries carry the kernel SYMBOL that ran, so they line up with rocprofv3's per-kernel rows
+            // profile entries carry the kernel SYMBOL that ran, so they line up with rocprofv3's per-kernel rows; `_lr` (here and in
+            // the fp32 label above) names the GemmLR instantiation of the kernel, which rocprofv3 prints as `...kernel<..., aid::GemmLR>`
             const char* sym = "aid_gemm_nt_kernel";
             e = aid::gemm_group_launch(g, dtype, static_cast<hipStream_t>(stream), &g_gemm_variant, &sym, problems[0].cu_share,
                                        has_lr ? &lr : nullptr);

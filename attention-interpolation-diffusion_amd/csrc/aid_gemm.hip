@@ -21,6 +21,9 @@
 //    launch_gemm() picks the engine per launch with a small cost model (long K loops + many tiles -> ping-pong).
 //  * aid_gemm_nt_kernel — edge path for ragged k (tests, odd context widths): 128x128 tile,
 //    register-staged, fully guarded loads, padded LDS rows.
+// The lock-step and the edge kernel carry a problem's low-rank segment (GemmLR, a second K segment before the epilogue): one kernel
+// each, the segment compiled in by the TYPE of the trailing kernel argument (GemmLR / NoLR).  Profile labels name the GemmLR
+// instantiation `<kernel>_lr`.
 #include "aid_common.hpp"
 #include "aid_kernels.hpp"
 
@@ -140,133 +143,12 @@ constexpr int GBM = 128, GBN = 128, GBK = 64;
 constexpr int GLD = GBK + 8;            // padded LDS row (elements)
 constexpr int GTHREADS = 256;
 
-template <typename T>
-__global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel(const GemmGroup g) {
-    typedef typename Vec<T>::v8 T8;
-    typedef typename Vec<T>::v4 T4;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    T* As = reinterpret_cast<T*>(smem_raw);                 // [2][GBM][GLD]
-    T* Bs = As + 2 * GBM * GLD;                             // [2][GBN][GLD]
-
-    const TileCoord tc = locate_tile<GBM, GBN>(g, blockIdx.x, gridDim.x);
-    const GemmDesc& P = g.p[tc.p];
-    const int m0 = tc.m0, n0 = tc.n0;
-    const T* __restrict__ A = reinterpret_cast<const T*>(P.a) + (int64_t)tc.batch * P.stride_a;
-    const T* __restrict__ B = reinterpret_cast<const T*>(P.b) + (int64_t)tc.batch * P.stride_b;
-    T* __restrict__ C = reinterpret_cast<T*>(P.c) + (int64_t)tc.batch * P.stride_c;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;   // wave tile origin inside the block tile
-    const int l31 = lane & 31, hi = lane >> 5;
-
-    // staging: 128 rows x 8 chunks(16 B) per operand tile = 1024 chunks, 4 per thread
-    const int srow = tid >> 3, scol = (tid & 7) * 8;         // + 32 rows per step
-    T8 ra[4], rb[4];
-
-    auto stage_load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = srow + 32 * i;
-            const bool kin = (k0 + scol) < P.k;
-            ra[i] = (kin && (m0 + r) < P.m) ? *reinterpret_cast<const T8*>(A + (int64_t)(m0 + r) * P.lda + k0 + scol)
-                                            : zero8<T>();
-            rb[i] = (kin && (n0 + r) < P.n) ? *reinterpret_cast<const T8*>(B + (int64_t)(n0 + r) * P.ldb + k0 + scol)
-                                            : zero8<T>();
-        }
-    };
-    auto stage_write = [&](int buf) {
-        T* as = As + buf * GBM * GLD;
-        T* bs = Bs + buf * GBN * GLD;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = srow + 32 * i;
-            *reinterpret_cast<T8*>(as + r * GLD + scol) = ra[i];
-            *reinterpret_cast<T8*>(bs + r * GLD + scol) = rb[i];
-        }
-    };
-
-    f32x16 acc[2][2];   // [n block][m block]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nk = (P.k + GBK - 1) / GBK;
-    stage_load(0);
-    stage_write(0);
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) stage_load((kt + 1) * GBK);
-        const T* as = As + buf * GBM * GLD + (wm + l31) * GLD + hi * 8;
-        const T* bs = Bs + buf * GBN * GLD + (wn + l31) * GLD + hi * 8;
-#pragma unroll
-        for (int ks = 0; ks < GBK / 16; ++ks) {
-            T8 fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                fa[i] = *reinterpret_cast<const T8*>(as + i * 32 * GLD + ks * 16);   // rows m
-                fb[i] = *reinterpret_cast<const T8*>(bs + i * 32 * GLD + ks * 16);   // rows n
-            }
-#pragma unroll
-            for (int in = 0; in < 2; ++in)
-#pragma unroll
-                for (int im = 0; im < 2; ++im)
-                    acc[in][im] = mfma32(fb[in], fa[im], acc[in][im]);              // D[n][m]
-        }
-        if (kt + 1 < nk) stage_write(buf ^ 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: lane (m = l31, hi) holds n = 8*g + 4*hi + {0..3} for g = r>>2 -------------
-    mfma_fence(acc);
-    const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
-#pragma unroll
-    for (int im = 0; im < 2; ++im) {
-        const int m = m0 + wm + im * 32 + l31;
-        if (m >= P.m) continue;
-#pragma unroll
-        for (int in = 0; in < 2; ++in) {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int n = n0 + wn + in * 32 + gq * 8 + hi * 4;
-                if (n >= P.n) continue;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[in][im][gq * 4 + e];
-                if (P.ln_stats) ln_fix4(P, P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats, m, n, v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= P.scale;
-                if (bias) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (n + e < P.n) v[e] += (float)bias[n + e];
-                }
-                if (P.residual) {                       // added after the first rounding, like the reference's separate add
-                    const T* R = reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c + (int64_t)m * P.ldc + n;
-                    const f32x4 r0 = up4<T>(cvt4<T>(v));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (n + e < P.n) ? r0[e] + (float)R[e] : 0.f;
-                }
-                // columns [n, round_up(n, 4)) are written with zeros (aid_hip.h): the guarded loads leave their accumulators 0, but the
-                // folded LayerNorm's fix-up (or a negative scale) does not keep them there
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e >= P.n) v[e] = 0.f;
-                *reinterpret_cast<T4*>(C + (int64_t)m * P.ldc + n) = cvt4<T>(v);
-            }
-        }
-    }
-}
-
-// The same tile with the problem's low-rank segment (GemmLR) run through a second K loop before the epilogue.  A copy on purpose:
-// with the kernel above turned into an instantiation of a shared template, its register allocation changed.
-template <typename T>
-__device__ __forceinline__ void gemm_edge_tile_lr(const GemmGroup& g, const GemmLR* lr) {
+// LRT = GemmLR: the problem's low-rank segment runs through a second K loop before the epilogue; LRT = NoLR: no segment.  One kernel,
+// and its body stays in the __global__ function: moved into a device function that takes the group by reference, the NoLR
+// instantiation compiles to other code (scalar register numbering, the epilogue's branch logic) than the kernel had before the segment
+// existed.  With the body here the only trace of the NoLR argument is its kernarg slot (DESIGN.md "LoRA").
+template <typename T, typename LRT>
+__global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel(const GemmGroup g, const LRT lr) {
     typedef typename Vec<T>::v8 T8;
     typedef typename Vec<T>::v4 T4;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -352,8 +234,8 @@ __device__ __forceinline__ void gemm_edge_tile_lr(const GemmGroup& g, const Gemm
         __syncthreads();
     }
 
-    {                                      // acc += LA LB^T: the same loop on the low-rank operands (k % 64 == 0)
-        const GemmLRDesc& L = lr->p[tc.p];
+    if constexpr (std::is_same<LRT, GemmLR>::value) {      // acc += LA LB^T: the same loop on the low-rank operands (k % 64 == 0)
+        const GemmLRDesc& L = lr.p[tc.p];
         const T* __restrict__ LA = reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a;
         const T* __restrict__ LB = reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b;
         auto lr_load = [&](int k0) {
@@ -419,12 +301,6 @@ __device__ __forceinline__ void gemm_edge_tile_lr(const GemmGroup& g, const Gemm
         }
     }
 }
-
-template <typename T>
-__global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel_lr(const GemmGroup g, const GemmLR lr) {
-    gemm_edge_tile_lr<T>(g, &lr);
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // Fast epilogue (tile columns inside the matrix, 16-byte aligned rows / pointers): straight-line code.
@@ -1596,8 +1472,10 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
 }
 
 // ---- one output tile per workgroup ------------------------------------------------------------------
-template <typename T, int BM, int BN, int BK, int NS, int WM, int WN>
-__global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const GemmGroup g) {
+// LRT = GemmLR: the low-rank segment rides along (NoLR: none).  mac() ends with no VMEM operation outstanding and the ring released, so
+// the segment is a second set_tile + mac over the LA / LB operands into the same accumulators.
+template <typename T, int BM, int BN, int BK, int NS, int WM, int WN, typename LRT>
+__global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const GemmGroup g, const LRT lr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const TileCoord tc = locate_tile<BM, BN>(g, blockIdx.x, gridDim.x);
     const GemmDesc& P = g.p[tc.p];
@@ -1609,30 +1487,13 @@ __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const Ge
     e.set_tile(P, A, B, tc.m0, tc.n0);
     e.zero_acc();
     e.mac(0, P.k / BK);
-    e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
-                     P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
-}
-
-// The same with the low-rank segment: mac() ends with no VMEM operation outstanding and the ring released, so the segment is a second
-// set_tile + mac over the LA / LB operands into the same accumulators.
-template <typename T, int BM, int BN, int BK, int NS, int WM, int WN>
-__global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel_lr(const GemmGroup g, const GemmLR lr) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const TileCoord tc = locate_tile<BM, BN>(g, blockIdx.x, gridDim.x);
-    const GemmDesc& P = g.p[tc.p];
-    const T* A = reinterpret_cast<const T*>(P.a) + (int64_t)tc.batch * P.stride_a;
-    const T* B = reinterpret_cast<const T*>(P.b) + (int64_t)tc.batch * P.stride_b;
-    T* C = reinterpret_cast<T*>(P.c) + (int64_t)tc.batch * P.stride_c;
-    Engine<T, BM, BN, BK, NS, WM, WN> e;
-    e.init(smem_raw);
-    e.set_tile(P, A, B, tc.m0, tc.n0);
-    e.zero_acc();
-    e.mac(0, P.k / BK);
-    const GemmLRDesc& L = lr.p[tc.p];
-    if (L.k > 0) {
-        e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
-                      reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
-        e.mac(0, L.k / BK);
+    if constexpr (std::is_same<LRT, GemmLR>::value) {
+        const GemmLRDesc& L = lr.p[tc.p];
+        if (L.k > 0) {
+            e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
+                          reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
+            e.mac(0, L.k / BK);
+        }
     }
     e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
                      P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
@@ -1641,51 +1502,29 @@ __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel_lr(const
 // ------------------------------------------------------------------------------------------------
 // Host side: plan_gemm picks the engine of a group and launches nothing; launch_plan runs the plan.
 // ------------------------------------------------------------------------------------------------
+static int tiles_of(const GemmDesc& d, int bm, int bn) { return ((d.m + bm - 1) / bm) * ((d.n + bn - 1) / bn) * d.batch; }
+
 static int count_tiles(const GemmGroup& g, int bm, int bn) {
     int tiles = 0;
-    for (int i = 0; i < g.n_problems; ++i) tiles += ((g.p[i].m + bm - 1) / bm) * ((g.p[i].n + bn - 1) / bn) * g.p[i].batch;
+    for (int i = 0; i < g.n_problems; ++i) tiles += tiles_of(g.p[i], bm, bn);
     return tiles;
 }
 
 // g.tile_start (the kernels' block -> problem map) in units of bm x bn tiles; returns the tile count
-static int fill_tile_start(GemmGroup& g, int bm, int bn) {
+int fill_tile_start(GemmGroup& g, int bm, int bn) {
     int tiles = 0;
     for (int i = 0; i < g.n_problems; ++i) {
         g.tile_start[i] = tiles;
-        tiles += ((g.p[i].m + bm - 1) / bm) * ((g.p[i].n + bn - 1) / bn) * g.p[i].batch;
+        tiles += tiles_of(g.p[i], bm, bn);
     }
     for (int i = g.n_problems; i <= AID_GEMM_MAX_PROBLEMS; ++i) g.tile_start[i] = tiles;
     return tiles;
 }
 
-template <typename K>
+// `lr` is the kernel's trailing argument: the problems' GemmLR, or NoLR{}
+template <typename K, typename LRT>
 static hipError_t launch_with_smem(K kernel, size_t smem, PerDevice<int>& attr_set, GemmGroup& g, int bm, int bn, hipStream_t stream,
-                                   int threads) {
-    const int tiles = fill_tile_start(g, bm, bn);
-    if (tiles <= 0) return hipSuccess;
-    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(kernel), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(threads), smem, stream, g);
-    return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t launch_edge(GemmGroup& g, hipStream_t stream) {
-    static PerDevice<int> attr_set;
-    return launch_with_smem(aid_gemm_nt_kernel<T>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), attr_set, g, GBM, GBN, stream, GTHREADS);
-}
-
-template <typename T, int NS>
-static hipError_t launch_pipe(GemmGroup& g, hipStream_t stream) {
-    static PerDevice<int> attr_set;
-    return launch_with_smem(aid_gemm_nt_pipe_kernel<T, 128, 128, 64, NS, 2, 4>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g,
-                            128, 128, stream, 512);
-}
-
-// the `_lr` kernels take the GemmLR next to the group
-template <typename K>
-static hipError_t launch_lr(K kernel, size_t smem, PerDevice<int>& attr_set, GemmGroup& g, const GemmLR& lr, int bm, int bn,
-                            hipStream_t stream, int threads) {
+                                   int threads, const LRT& lr) {
     const int tiles = fill_tile_start(g, bm, bn);
     if (tiles <= 0) return hipSuccess;
     const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(kernel), smem);
@@ -1694,17 +1533,18 @@ static hipError_t launch_lr(K kernel, size_t smem, PerDevice<int>& attr_set, Gem
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t launch_edge_lr(GemmGroup& g, const GemmLR& lr, hipStream_t stream) {
+template <typename T, typename LRT>
+static hipError_t launch_edge(GemmGroup& g, hipStream_t stream, const LRT& lr) {
     static PerDevice<int> attr_set;
-    return launch_lr(aid_gemm_nt_kernel_lr<T>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), attr_set, g, lr, GBM, GBN, stream, GTHREADS);
+    return launch_with_smem(aid_gemm_nt_kernel<T, LRT>, (size_t)2 * (GBM + GBN) * GLD * sizeof(T), attr_set, g, GBM, GBN, stream, GTHREADS,
+                            lr);
 }
 
-template <typename T, int NS>
-static hipError_t launch_pipe_lr(GemmGroup& g, const GemmLR& lr, hipStream_t stream) {
+template <typename T, int NS, typename LRT>
+static hipError_t launch_pipe(GemmGroup& g, hipStream_t stream, const LRT& lr) {
     static PerDevice<int> attr_set;
-    return launch_lr(aid_gemm_nt_pipe_kernel_lr<T, 128, 128, 64, NS, 2, 4>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g, lr,
-                     128, 128, stream, 512);
+    return launch_with_smem(aid_gemm_nt_pipe_kernel<T, 128, 128, 64, NS, 2, 4, LRT>, Engine<T, 128, 128, 64, NS, 2, 4>::SMEM, attr_set, g,
+                            128, 128, stream, 512, lr);
 }
 
 template <typename T, int PPV>
@@ -1793,7 +1633,7 @@ struct GemmPlan {
     const char* variant;                    // aid_last_gemm_variant()
     const char* symbol;                     // kernel symbol, for the profile entries
     bool writes_trans;                      // the engine writes the C of a trans_rows problem itself
-    bool lr;                                // the group carries low-rank segments: the `_lr` kernel of the engine runs
+    bool lr;                                // the group carries low-rank segments: the GemmLR instantiation of the engine's kernel runs
 };
 
 static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide& sd, int ncu, int n_big = 0, int n_small = 0,
@@ -1828,6 +1668,7 @@ static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide&
             pl.symbol = "aid_gemm_rs_kernel";
             break;
     }
+    // `_lr` names the GemmLR instantiation of the kernel (a profiler shows it as `...kernel<..., aid::GemmLR>`)
     if (lr) pl.symbol = engine == GemmEngine::Edge ? "aid_gemm_nt_kernel_lr" : "aid_gemm_nt_pipe_kernel_lr";
     // transposed C: the row-stationary engine and the 288-row tiles write it; side tiles run on the 128 x 128 engine, which does not
     pl.writes_trans = engine == GemmEngine::Rowstat || engine == GemmEngine::Pp288;
@@ -1948,18 +1789,12 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool 
 
 template <typename T>
 static hipError_t launch_plan(GemmPlan& pl, hipStream_t stream, const GemmLR* lr) {
-    if (pl.lr) {
-        switch (pl.engine) {
-            case GemmEngine::Edge:      return launch_edge_lr<T>(pl.g, *lr, stream);
-            case GemmEngine::Lockstep:  return launch_pipe_lr<T, 2>(pl.g, *lr, stream);
-            case GemmEngine::Lockstep4: return launch_pipe_lr<T, 4>(pl.g, *lr, stream);
-            default:                    return hipErrorInvalidValue;     // plan_gemm never plans another engine for it
-        }
-    }
+    const bool carries_lr = pl.engine == GemmEngine::Edge || pl.engine == GemmEngine::Lockstep || pl.engine == GemmEngine::Lockstep4;
+    if (pl.lr && !carries_lr) return hipErrorInvalidValue;             // plan_gemm never plans another engine for a segment
     switch (pl.engine) {
-        case GemmEngine::Edge:      return launch_edge<T>(pl.g, stream);
-        case GemmEngine::Lockstep:  return launch_pipe<T, 2>(pl.g, stream);
-        case GemmEngine::Lockstep4: return launch_pipe<T, 4>(pl.g, stream);
+        case GemmEngine::Edge:      return pl.lr ? launch_edge<T>(pl.g, stream, *lr) : launch_edge<T>(pl.g, stream, NoLR{});
+        case GemmEngine::Lockstep:  return pl.lr ? launch_pipe<T, 2>(pl.g, stream, *lr) : launch_pipe<T, 2>(pl.g, stream, NoLR{});
+        case GemmEngine::Lockstep4: return pl.lr ? launch_pipe<T, 4>(pl.g, stream, *lr) : launch_pipe<T, 4>(pl.g, stream, NoLR{});
         case GemmEngine::Pp256:
         case GemmEngine::Pp256Tail: return launch_pp<T>(pl.g, stream, pl.n_big, pl.n_small, pl.sd);
         case GemmEngine::Pp288:     return launch_ppx<T>(pl.g, stream, pl.sd);

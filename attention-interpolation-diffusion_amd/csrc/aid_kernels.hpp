@@ -35,8 +35,9 @@ struct GemmGroup {                        // passed by value as the kernel argum
 };
 
 // Low-rank second K segment of a problem (AidGemmProblem.lr_*): acc += LA[m0.., 0:k] LB[n0.., 0:k]^T after the main K loop, before
-// the epilogue.  A kernel argument of its own, next to the GemmGroup, of the `_lr` kernel instantiations only: the kernels without it
-// keep their arguments and code.  Entry i belongs to GemmGroup.p[i] (k = 0: none).
+// the epilogue.  Entry i belongs to GemmGroup.p[i] (k = 0: none).  The edge, lock-step and fp32 GEMM kernels take it as a trailing
+// by-value kernel argument whose TYPE compiles the segment in: GemmLR = with the segment (the profile labels call that instantiation
+// `<kernel>_lr`), NoLR = without.
 struct GemmLRDesc {
     const void* a;                                    // [m, k] (row stride lda), batch b at a + b * stride_a
     const void* b;                                    // [n, k] (row stride ldb)
@@ -46,6 +47,10 @@ struct GemmLRDesc {
 struct GemmLR {
     GemmLRDesc p[AID_GEMM_MAX_PROBLEMS];
 };
+struct NoLR {};                                       // no low-rank segment
+
+// fills g.tile_start (the kernels' block -> problem map) in units of bm x bn tiles and returns the tile count (aid_gemm.hip)
+int fill_tile_start(GemmGroup& g, int bm, int bn);
 
 // Side problems of a ping-pong launch: the few short problems of a group whose K loop differs from the main ones (the
 // K = 2048 text-context projections next to the K = 1280 query projection of a cross-attention layer).  They run as
