@@ -15,6 +15,7 @@
 namespace {
 
 thread_local char g_err[256] = "";
+thread_local aid::AttnPlan g_attn_plan;            // of this thread's last attention call: g_variant points into it
 thread_local const char* g_variant = "";
 thread_local const char* g_gemm_variant = "";
 
@@ -473,65 +474,23 @@ int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
     const double per_seg = 4.0 * a.s * (double)a.l * c;
     const double flops = per_seg * ((double)segs * (a.n_frames - a.n_plain) + a.n_plain);
     const double flops_exec = a.seg_executed > 0 ? per_seg * a.seg_executed : flops;
-    const double bytes = 2.0 * (2.0 * a.n_frames * a.s * c + 2.0 * a.n_kv * a.l * c);
+    const double bytes = (a.dtype == AID_DTYPE_F32 ? 4.0 : 2.0) * (2.0 * a.n_frames * a.s * c + 2.0 * a.n_kv * a.l * c);
+    // which kernel(s), their names and their shares of the call: aid::plan_attn (aid_attn.hip).  A split call is two launches: the
+    // frames with one key segment (one segment's work each, all of it executed), then the rest of the call's work on the other frames.
+    const aid::AttnPlan& pl = g_attn_plan = aid::plan_attn(a);
+    const double f_single = per_seg * pl.n_single;
+    const struct { double flops, bytes, flops_exec; } work[3] = {        // indexed by aid::AttnShare
+        {flops, bytes, flops_exec},
+        {f_single, bytes * pl.n_single / a.n_frames, f_single},
+        {flops - f_single, bytes * (a.n_frames - pl.n_single) / a.n_frames, flops_exec - f_single}};
     hipError_t e = hipSuccess;
-    if (a.dtype == AID_DTYPE_F32) {             // float32 storage: one correctness-first kernel for every mode (aid_f32.hip)
-        char nm[64];
-        snprintf(nm, sizeof(nm), "aid_attn_f32<d%d,%s>", a.d, a.mode == AID_MODE_PLAIN ? "plain" : a.mode == AID_MODE_INNER ? "inner" : "outer");
-        {
-            ProfScope ps(static_cast<hipStream_t>(stream), nm, flops, 2.0 * bytes, flops_exec);
-            e = aid::attn_f32_launch(a, static_cast<hipStream_t>(stream));
-        }
-        g_variant = "aid_attn_f32";
-        return e == hipSuccess ? AID_OK : fail_hip(e, "aid_attn_fwd");
+    for (int i = 0; i < pl.n_steps && e == hipSuccess; ++i) {
+        const aid::AttnStep& st = pl.step[i];
+        const auto& w = work[static_cast<int>(st.share)];
+        ProfScope ps(static_cast<hipStream_t>(stream), st.label, w.flops, w.bytes, w.flops_exec);
+        e = aid::launch_attn_plan(a, st, static_cast<hipStream_t>(stream));
     }
-    // d = 64, whole key tiles: the ping-pong kernel (aid_attn_pp.hip).  It runs every kind of frame — one key segment (PLAIN, riders,
-    // fused end points), two (fused INNER, one-sided OUTER), three (fused OUTER) — deciding per frame ON THE DEVICE from the
-    // coefficients like aid_attn_kernel; the host-side counts below only attribute the work.
-    //   default: calls it can run ALONE (several segments per frame: multiples of 512 keys), fused OUTER and INNER from 1024 keys, PLAIN
-    //   and pure OUTER from 2048 — same-process A/B, us: S = 4096 plain 648 -> 588, outer 1160 -> 1078, inner 915 -> 860; S = 1024 outer
-    //   163.5 -> 161.1, inner 130.6 -> 135.3, plain 93 -> 110 (a 16-tile stream on one workgroup per CU; profiles/r03_attn_notes.txt).
-    //   ATTN_V2 = 0 never; 1 wherever supported (tests) — a call it cannot run alone is then split: single-segment frames here, the
-    //   others on aid_attn_kernel in a second launch.
-    const int n_single = a.mode == AID_MODE_PLAIN ? a.n_frames : a.n_plain + ((a.fused && a.n_frames - a.n_plain >= 2) ? 2 : 0);
-    // (a call with several segments per frame: segments of whole 8-tile trips; INNER: k2 / vt2 present)
-    const bool alone = a.mode == AID_MODE_PLAIN || (a.l % 512 == 0 && (a.mode == AID_MODE_OUTER || (a.k2 && a.vt2)));
-    const bool dflt = a.l >= ((a.mode == AID_MODE_PLAIN || (a.mode == AID_MODE_OUTER && !a.fused)) ? 2048 : 1024);
-    const int v2 = aid::tune(aid::TUNE_ATTN_V2);
-    // text keys (<= 96 per segment: the cross-attention of the SDXL stack): every segment resident in LDS, independent waves, online
-    // softmax over the segment's <= 3 score tiles, OUTER sides combined from the segments' maxima and row sums (aid_attn_tx.hip).  The
-    // default wherever it applies (profiles/r05_attn_tx_notes.txt); ATTN_TX = 0 keeps these calls on aid_attn_kernel.  (Round 4's
-    // short-stream ping-pong kernel, aid_attn_xs.hip, measured 5 - 20 % slower than aid_attn_kernel and was removed in round 5.)
-    if (!a.bias && aid::tune(aid::TUNE_ATTN_TX) != 0 && v2 != 1 && aid::attn_tx_supported(a)) {
-        char nm[64];
-        static const char* const mn[] = {"plain", "inner", "outer"};
-        snprintf(nm, sizeof(nm), "aid_attn_tx<%s,d64,%s>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", mn[a.mode]);
-        {
-            ProfScope ps(static_cast<hipStream_t>(stream), nm, flops, bytes, flops_exec);
-            e = aid::attn_tx_launch(a, static_cast<hipStream_t>(stream));
-        }
-        g_variant = a.mode == AID_MODE_OUTER ? "aid_attn_tx<d64,outer>" : a.mode == AID_MODE_INNER ? "aid_attn_tx<d64,inner>" : "aid_attn_tx<d64,plain>";
-        return e == hipSuccess ? AID_OK : fail_hip(e, "aid_attn_fwd");
-    }
-    const bool use_pp = !a.bias && aid::attn_pp_supported(a) && (alone || n_single > 0) &&   // (a score bias: aid_attn_kernel's BIAS instantiation)
-                        (v2 == 1 || (v2 < 0 && alone && dflt));
-    if (use_pp) {
-        char nm[64];
-        snprintf(nm, sizeof(nm), "aid_attn_pp<%s,d64%s>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16",
-                 a.mode == AID_MODE_PLAIN ? "" : !alone ? ",riders" : a.mode == AID_MODE_OUTER ? ",outer" : ",inner");
-        const double f1 = alone ? flops : per_seg * n_single;
-        ProfScope ps(static_cast<hipStream_t>(stream), nm, f1, alone ? bytes : bytes * n_single / a.n_frames,
-                     alone ? flops_exec : f1);
-        e = aid::attn_pp_launch(a, static_cast<hipStream_t>(stream), alone);
-        g_variant = !alone || a.mode == AID_MODE_PLAIN ? "aid_attn_pp<d64>" : a.mode == AID_MODE_OUTER ? "aid_attn_pp<d64,outer>" : "aid_attn_pp<d64,inner>";
-    }
-    if (e == hipSuccess && !(use_pp && alone)) {
-        const char* nm = aid::attn_variant_name(a);
-        const double fa = use_pp ? flops - per_seg * n_single : flops;
-        const double fx = use_pp ? flops_exec - per_seg * n_single : flops_exec;
-        ProfScope ps(static_cast<hipStream_t>(stream), nm, fa, use_pp ? bytes * (a.n_frames - n_single) / a.n_frames : bytes, fx);
-        e = aid::attn_launch(a, static_cast<hipStream_t>(stream), &g_variant, use_pp);
-    }
+    g_variant = pl.variant;
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_attn_fwd");
 }
 

@@ -45,10 +45,10 @@
 // OUTER shares the own-keys segment between its two softmaxes (3 segment passes, not 4): the online
 // state after the own segment is snapshotted and continued once with the begin and once with the
 // end frame; frames with coefficient exactly 0 / 1 skip the zero-weighted side.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
-
 
 #include "aid_common.hpp"
 #include "aid_kernels.hpp"
@@ -1189,53 +1189,30 @@ static bool attn_res(const AidAttnArgs& a) {
     return a.d == 40;           // measured in the stacks: d = 40 -25 % (inner) / -14 % (plain); d = 64 / 80 within +-5 % of streaming
 }
 
+// The one map from a planned variant to its instantiation.  The set per (T, D, MODE) is closed — base, BIAS; RES and NW8 for D <= 80; QB2 for
+// D = 40 PLAIN; PIPE for D = 40 and D = 64 PLAIN: the collapsing template arguments turn every other branch into the base kernel again.
 template <typename T, int D, int MODE>
-static hipError_t launch_nw(AttnKParams& p, hipStream_t stream) {
-    p.q_iters = 1;
-    if (p.a.bias) {                                             // score bias: the one instantiation that reads it
-        p.nqb = (p.a.s + 127) / 128;
-        return launch_variant<T, D, MODE, 4, 1, false, false, true>(p, stream);
-    }
-    if (D <= 80 && attn_res(p.a)) {
-        const int nqb = (p.a.s + 127) / 128;                    // 128-row blocks (4 waves x 32 rows)
-        int chunks = nqb / 2 < 1 ? 1 : nqb / 2 > RES_CHUNKS_MAX ? RES_CHUNKS_MAX : nqb / 2;
-        if (tune(TUNE_ATTN_RES_CHUNKS) > 0) chunks = tune(TUNE_ATTN_RES_CHUNKS);
-        p.nqb = nqb < chunks ? nqb : chunks;
-        p.q_iters = (nqb + p.nqb - 1) / p.nqb;
-        return launch_variant<T, D, MODE, 4, 1, false, (D <= 80)>(p, stream);
-    }
-    if (D == 40 && MODE == AID_MODE_PLAIN && attn_qb(p.a) == 2) {
-        p.nqb = (p.a.s + 255) / 256;
-        return launch_variant<T, D, MODE, 4, (D == 40 && MODE == AID_MODE_PLAIN) ? 2 : 1, false>(p, stream);
-    }
-    p.nqb = (p.a.s + 127) / 128;
-    constexpr bool CAN_PIPE = D == 40 || (D == 64 && MODE == AID_MODE_PLAIN);
-    if (D <= 80 && attn_nw(p.a) == 8) {
-        p.nqb = (p.a.s + 255) / 256;
-        return launch_variant<T, D, MODE, (D <= 80) ? 8 : 4, 1, false>(p, stream);
-    }
-    if (CAN_PIPE && attn_pipe(p.a)) return launch_variant<T, D, MODE, 4, 1, CAN_PIPE>(p, stream);
-    return launch_variant<T, D, MODE, 4, 1, false>(p, stream);
-}
-
-template <typename T, int D>
-static hipError_t launch_mode(AttnKParams& p, hipStream_t stream) {
-    switch (p.a.mode) {
-        case AID_MODE_PLAIN: return launch_nw<T, D, AID_MODE_PLAIN>(p, stream);
-        case AID_MODE_INNER: return launch_nw<T, D, AID_MODE_INNER>(p, stream);
-        default:             return launch_nw<T, D, AID_MODE_OUTER>(p, stream);
-    }
+static hipError_t launch_order(const AttnStep& st, const AttnKParams& p, hipStream_t stream) {
+    constexpr bool SMALL = D <= 80, QB2 = D == 40 && MODE == AID_MODE_PLAIN, CAN_PIPE = D == 40 || (D == 64 && MODE == AID_MODE_PLAIN);
+    if (st.bias)             return launch_variant<T, D, MODE, 4, 1, false, false, true>(p, stream);
+    if (SMALL && st.res)     return launch_variant<T, D, MODE, 4, 1, false, SMALL>(p, stream);
+    if (QB2 && st.qb == 2)   return launch_variant<T, D, MODE, 4, QB2 ? 2 : 1, false>(p, stream);
+    if (SMALL && st.nw == 8) return launch_variant<T, D, MODE, SMALL ? 8 : 4, 1, false>(p, stream);
+    if (CAN_PIPE && st.pipe) return launch_variant<T, D, MODE, 4, 1, CAN_PIPE>(p, stream);
+    const bool base = st.nw == 4 && st.qb == 1 && !st.pipe && !st.res;            // anything else is not built (plan_attn plans none)
+    return base ? launch_variant<T, D, MODE, 4, 1, false>(p, stream) : hipErrorInvalidValue;
 }
 
 template <typename T>
-static hipError_t launch_d(AttnKParams& p, hipStream_t stream) {
-    switch (p.a.d) {
-        case 40:  return launch_mode<T, 40>(p, stream);
-        case 64:  return launch_mode<T, 64>(p, stream);
-        case 80:  return launch_mode<T, 80>(p, stream);
-        case 160: return launch_mode<T, 160>(p, stream);
-        default:  return hipErrorInvalidValue;
-    }
+static hipError_t launch_order(const AttnStep& st, const AttnKParams& p, hipStream_t stream) {
+    static_assert(AID_MODE_PLAIN == 0 && AID_MODE_INNER == 1 && AID_MODE_OUTER == 2, "mode index");
+    typedef hipError_t (*Fn)(const AttnStep&, const AttnKParams&, hipStream_t);
+    static const Fn by_d_mode[4][3] = {{launch_order<T, 40, 0>, launch_order<T, 40, 1>, launch_order<T, 40, 2>},
+                                       {launch_order<T, 64, 0>, launch_order<T, 64, 1>, launch_order<T, 64, 2>},
+                                       {launch_order<T, 80, 0>, launch_order<T, 80, 1>, launch_order<T, 80, 2>},
+                                       {launch_order<T, 160, 0>, launch_order<T, 160, 1>, launch_order<T, 160, 2>}};
+    const int di = p.a.d == 40 ? 0 : p.a.d == 64 ? 1 : p.a.d == 80 ? 2 : p.a.d == 160 ? 3 : -1;
+    return di < 0 ? hipErrorInvalidValue : by_d_mode[di][p.a.mode](st, p, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1284,36 +1261,84 @@ hipError_t lerp_kv_launch(const void* k, const void* vt, void* k2, void* vt2, co
 
 bool attn_head_dim_supported(int d) { return d == 40 || d == 64 || d == 80 || d == 160; }
 
-const char* attn_variant_name(const AidAttnArgs& a) {
-    static thread_local char name[64];
-    static const char* modes[] = {"plain", "inner", "outer"};
-    if (a.bias)
-        snprintf(name, sizeof(name), "aid_attn<%s,d%d,%s,nw4,bias>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", a.d, modes[a.mode]);
-    else if (attn_res(a))
-        snprintf(name, sizeof(name), "aid_attn<%s,d%d,%s,res>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", a.d, modes[a.mode]);
-    else if (attn_qb(a) == 2)
-        snprintf(name, sizeof(name), "aid_attn<%s,d%d,%s,nw%d,qb2>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", a.d,
-                 modes[a.mode], attn_nw(a));
-    else if (attn_nw(a) != 8 && attn_pipe(a))
-        snprintf(name, sizeof(name), "aid_attn<%s,d%d,%s,nw%d,pipe>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", a.d,
-                 modes[a.mode], attn_nw(a));
-    else
-        snprintf(name, sizeof(name), "aid_attn<%s,d%d,%s,nw%d>", a.dtype == AID_DTYPE_F16 ? "f16" : "bf16", a.d,
-                 modes[a.mode], attn_nw(a));
-    return name;
+// Host side: plan_attn picks the kernel(s) of a call and launches nothing; launch_attn_plan runs one step of the plan.  The profile
+// labels and the aid_last_attn_variant() string come out of the plan: this is the one place that names an attention kernel.
+AttnPlan plan_attn(const AidAttnArgs& a) {
+    const char* const mode = a.mode == AID_MODE_PLAIN ? "plain" : a.mode == AID_MODE_INNER ? "inner" : "outer";
+    const char* const dt = a.dtype == AID_DTYPE_F16 ? "f16" : "bf16";
+    AttnPlan pl;
+    AttnStep* st = &pl.step[0];
+    pl.n_single = a.mode == AID_MODE_PLAIN ? a.n_frames : a.n_plain + ((a.fused && a.n_frames - a.n_plain >= 2) ? 2 : 0);
+    if (a.dtype == AID_DTYPE_F32) {             // float32 storage: one correctness-first kernel for every mode (aid_f32.hip)
+        st->engine = AttnEngine::F32;
+        snprintf(st->label, sizeof(st->label), "aid_attn_f32<d%d,%s>", a.d, mode);
+        snprintf(pl.variant, sizeof(pl.variant), "aid_attn_f32");
+        return pl;
+    }
+    const int v2 = tune(TUNE_ATTN_V2);
+    // text keys (<= 96 per segment: the cross-attention of the SDXL stack): every segment resident in LDS, independent waves, online
+    // softmax over the segment's <= 3 score tiles, OUTER sides combined from the segments' maxima and row sums (aid_attn_tx.hip).  The
+    // default wherever it applies (profiles/r05_attn_tx_notes.txt); ATTN_TX = 0 keeps these calls on aid_attn_kernel.  (Round 4's
+    // short-stream ping-pong kernel, aid_attn_xs.hip, measured 5 - 20 % slower than aid_attn_kernel and was removed in round 5.)
+    if (!a.bias && tune(TUNE_ATTN_TX) != 0 && v2 != 1 && attn_tx_supported(a)) {
+        st->engine = AttnEngine::Tx;
+        snprintf(st->label, sizeof(st->label), "aid_attn_tx<%s,d64,%s>", dt, mode);
+        snprintf(pl.variant, sizeof(pl.variant), "aid_attn_tx<d64,%s>", mode);
+        return pl;
+    }
+    // d = 64, whole key tiles: the ping-pong kernel (aid_attn_pp.hip).  It runs every kind of frame — one key segment (PLAIN, riders,
+    // fused end points), two (fused INNER, one-sided OUTER), three (fused OUTER) — deciding per frame ON THE DEVICE from the
+    // coefficients like aid_attn_kernel; the host-side n_single only attributes the work.
+    //   default: calls it can run ALONE (several segments per frame: multiples of 512 keys), fused OUTER and INNER from 1024 keys, PLAIN
+    //   and pure OUTER from 2048 — same-process A/B, us: S = 4096 plain 648 -> 588, outer 1160 -> 1078, inner 915 -> 860; S = 1024 outer
+    //   163.5 -> 161.1, inner 130.6 -> 135.3, plain 93 -> 110 (a 16-tile stream on one workgroup per CU; profiles/r03_attn_notes.txt).
+    //   ATTN_V2 = 0 never; 1 wherever supported (tests) — a call it cannot run alone is then split: single-segment frames on it, the
+    //   others on aid_attn_kernel in a second launch.
+    // (a call with several segments per frame: segments of whole 8-tile trips; INNER: k2 / vt2 present)
+    const bool alone = a.mode == AID_MODE_PLAIN || (a.l % 512 == 0 && (a.mode == AID_MODE_OUTER || (a.k2 && a.vt2)));
+    const bool dflt = a.l >= ((a.mode == AID_MODE_PLAIN || (a.mode == AID_MODE_OUTER && !a.fused)) ? 2048 : 1024);
+    if (!a.bias && attn_pp_supported(a) && (alone || pl.n_single > 0) &&   // (a score bias: aid_attn_kernel's BIAS instantiation)
+        (v2 == 1 || (v2 < 0 && alone && dflt))) {
+        const char* const kind = a.mode == AID_MODE_PLAIN ? "" : a.mode == AID_MODE_OUTER ? ",outer" : ",inner";
+        st->engine = AttnEngine::Pp;
+        st->share = alone ? AttnShare::All : AttnShare::Single;
+        snprintf(st->label, sizeof(st->label), "aid_attn_pp<%s,d64%s>", dt, alone ? kind : ",riders");
+        snprintf(pl.variant, sizeof(pl.variant), "aid_attn_pp<d64%s>", kind);
+        if (alone) return pl;
+        st = &pl.step[pl.n_steps++];                             // the other frames: a second launch, which names the call
+        st->share = AttnShare::Rest;
+    }
+    // The program-order kernel's variant, BIAS -> RES -> QB2 -> NW8 -> PIPE -> base (the knob rules above), and the geometry that goes with it
+    if (a.bias) st->bias = true;                                 // score bias: the one instantiation that reads it
+    else if (attn_res(a)) st->res = true;
+    else if (attn_qb(a) == 2) st->qb = 2;
+    else if (attn_nw(a) == 8) st->nw = 8;
+    else if (attn_pipe(a)) st->pipe = true;
+    const int rows = 32 * st->nw * st->qb;                       // query rows per workgroup: 128, or 256 (NW8, QB2)
+    const int nqb = (a.s + rows - 1) / rows;
+    st->nqb = nqb;
+    if (st->res) {                                               // a workgroup works through a chunk of the 128-row blocks
+        int chunks = nqb / 2 < 1 ? 1 : nqb / 2 > RES_CHUNKS_MAX ? RES_CHUNKS_MAX : nqb / 2;
+        if (tune(TUNE_ATTN_RES_CHUNKS) > 0) chunks = tune(TUNE_ATTN_RES_CHUNKS);
+        st->nqb = nqb < chunks ? nqb : chunks;
+        st->q_iters = (nqb + st->nqb - 1) / st->nqb;
+    }
+    snprintf(st->label, sizeof(st->label), "aid_attn<%s,d%d,%s,%s%s>", dt, a.d, mode, st->res ? "res" : st->nw == 8 ? "nw8" : "nw4",
+             st->bias ? ",bias" : st->qb == 2 ? ",qb2" : st->pipe ? ",pipe" : "");
+    snprintf(pl.variant, sizeof(pl.variant), "%s", st->label);
+    return pl;
 }
 
-hipError_t attn_launch(const AidAttnArgs& a, hipStream_t stream, const char** variant, bool skip_single) {
-    AttnKParams p;
-    p.a = a;
-    p.nqb = 0;
-    p.q_iters = 1;
-    p.skip_single = skip_single ? 1 : 0;
+hipError_t launch_attn_plan(const AidAttnArgs& a, const AttnStep& st, hipStream_t stream) {
+    switch (st.engine) {
+        case AttnEngine::F32: return attn_f32_launch(a, stream);
+        case AttnEngine::Tx:  return attn_tx_launch(a, stream);
+        case AttnEngine::Pp:  return attn_pp_launch(a, stream, st.share == AttnShare::All);
+        case AttnEngine::Order: break;
+    }
+    AttnKParams p = {a, st.nqb, a.softmax_scale * 1.4426950408889634f, st.q_iters, st.share == AttnShare::Rest ? 1 : 0};
     if (tune(TUNE_ATTN_ORDER) == 0) p.a.n_plain = 0;         // development knob: plain XCD order for mixed launches
-    p.c2 = a.softmax_scale * 1.4426950408889634f;
-    hipError_t e = (a.dtype == AID_DTYPE_F16) ? launch_d<f16>(p, stream) : launch_d<bf16>(p, stream);
-    if (variant) *variant = attn_variant_name(a);
-    return e;
+    return a.dtype == AID_DTYPE_F16 ? launch_order<f16>(st, p, stream) : launch_order<bf16>(st, p, stream);
 }
 
 }  // namespace aid

@@ -105,9 +105,25 @@ hipError_t attn_f32_launch(const AidAttnArgs& a, hipStream_t stream);
 hipError_t lerp_kv_f32_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                               int end, int64_t k_fs, int64_t vt_fs, hipStream_t stream);
 
-// attention core; returns hipSuccess / error, writes the variant name for profiling
-// skip_single: the frames with ONE key segment are left to the ping-pong kernel (attn_pp_launch on the same stream)
-hipError_t attn_launch(const AidAttnArgs& a, hipStream_t stream, const char** variant, bool skip_single = false);
+// attention core: plan_attn picks the kernel(s) of a call and launches nothing; launch_attn_plan runs one step of the plan (aid_attn.hip)
+enum class AttnEngine { F32, Tx, Pp, Order };         // aid_f32.hip, aid_attn_tx.hip, aid_attn_pp.hip, aid_attn_kernel (program order)
+enum class AttnShare { All = 0, Single = 1, Rest = 2 };   // what a step runs: the whole call; the frames with ONE key segment; the others
+struct AttnStep {
+    AttnEngine engine = AttnEngine::Order;
+    AttnShare  share = AttnShare::All;                // Pp + Single, then Order + Rest (AttnKParams.skip_single): the two launches of a split call
+    int  nw = 4, qb = 1;                              // Order, the variant: waves per workgroup, 32-row query blocks per wave, software-
+    bool pipe = false, res = false, bias = false;     //   pipelined loop, resident key segments, score bias (at most one differs from these)
+    int  nqb = 0, q_iters = 1;                        // Order: workgroups per (frame, head), query blocks each works through
+    char label[64] = "";                              // profile entry (AidProfileEntry.kernel)
+};
+struct AttnPlan {
+    int      n_steps = 1;
+    AttnStep step[2];
+    int      n_single = 0;                            // frames of the call with ONE key segment (work attribution of a split call)
+    char     variant[64] = "";                        // aid_last_attn_variant()
+};
+AttnPlan   plan_attn(const AidAttnArgs& a);
+hipError_t launch_attn_plan(const AidAttnArgs& a, const AttnStep& st, hipStream_t stream);
 // d = 64 ping-pong kernel for the single-segment frames of a call (aid_attn_pp.hip); frames with more segments exit at once
 bool       attn_pp_supported(const AidAttnArgs& a);
 hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi);
@@ -117,7 +133,6 @@ hipError_t attn_tx_launch(const AidAttnArgs& a, hipStream_t stream);
 bool       attn_head_dim_supported(int d);
 hipError_t lerp_kv_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                           int end, int64_t k_fs, int64_t vt_fs, int dtype, hipStream_t stream);
-const char* attn_variant_name(const AidAttnArgs& a);   // thread-local buffer
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,
                             int dtype, hipStream_t stream);
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);

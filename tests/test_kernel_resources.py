@@ -62,7 +62,7 @@ def test_attention_variants_keep_the_waves_per_simd_the_launcher_assumes():
     a = _attn(_table("aid_attn"))
     assert len(a) >= 60
     for dt in ("f16", "bf16"):
-        # the variants the two bench stacks launch (launch_nw / attn_nw / attn_qb / attn_pipe / attn_res in aid_attn.hip)
+        # the variants the two bench stacks launch (plan_attn / attn_nw / attn_qb / attn_pipe / attn_res in aid_attn.hip)
         want = {
             (dt, 64, "p", 4, 1, False, False): 3,      # SDXL PLAIN: three waves per SIMD
             (dt, 64, "o", 8, 1, False, False): 2,      # SDXL OUTER, L >= 2048

@@ -3,6 +3,8 @@
 
 Make the inputs with the Makefile's flags plus `--cuda-device-only -S`, one file per build:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffast-math -fno-finite-math-only --cuda-device-only -S csrc/aid_gemm.hip -o new.s
+The attention objects take the extra flags csrc/Makefile gives them: `-mllvm -amdgpu-mfma-vgpr-form=1 -ffinite-math-only` for aid_attn.hip
+and aid_attn_pp.hip, `-mllvm -amdgpu-mfma-vgpr-form=1` alone for aid_attn_tx.hip.
 Per function symbol the instruction stream is kept (comments and directives dropped, local label numbers normalised).  Symbols are
 paired after removing what only names the low-rank variant of a GEMM kernel: a `_lr` suffix of the kernel name and the NoLR / GemmLR
 template argument; a kernel with the segment (GemmLR anywhere in its symbol) only pairs with one that has it too.  Prints SAME or DIFF
