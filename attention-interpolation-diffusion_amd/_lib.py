@@ -15,7 +15,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AID_LIB_PATH") or os.path.join(PKG_DIR, "libaid_hip.so")   # override: development A/B builds
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 
-AID_ABI_VERSION = 9
+AID_ABI_VERSION = 10
 DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 0, 1, 2
 MODE_PLAIN, MODE_INNER, MODE_OUTER = 0, 1, 2
 GEMM_MAX_PROBLEMS = 6
@@ -23,7 +23,7 @@ IP_NONE, IP_SAME, IP_PLAIN = 0, 1, 2
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
-    "aid_gemm_nt", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_processor_workspace_bytes", "aid_processor_fwd",
+    "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_processor_workspace_bytes", "aid_processor_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -41,7 +41,8 @@ class AidGemmProblem(C.Structure):
         ("ln_side", C.c_int32), ("trans_rows", C.c_int32), ("stride_stats", C.c_int64),
         ("cu_share", C.c_int32), ("reserved0", C.c_int32),
         ("lr_a", C.c_void_p), ("lr_b", C.c_void_p), ("lr_k", C.c_int32), ("lr_lda", C.c_int32), ("lr_ldb", C.c_int32),
-        ("reserved1", C.c_int32), ("lr_stride_a", C.c_int64), ("lr_stride_b", C.c_int64),
+        ("lr_scale_side", C.c_int32), ("lr_stride_a", C.c_int64), ("lr_stride_b", C.c_int64),
+        ("lr_row_scale", C.c_void_p),
     ]
 
 
@@ -85,6 +86,7 @@ class AidProcessorArgs(C.Structure):
         ("lora_down_x", C.c_void_p), ("lora_down_ctx", C.c_void_p), ("lora_down_o", C.c_void_p),
         ("lora_up_q", C.c_void_p), ("lora_up_k", C.c_void_p), ("lora_up_v", C.c_void_p), ("lora_up_o", C.c_void_p),
         ("lora_r_q", C.c_int32), ("lora_r_k", C.c_int32), ("lora_r_v", C.c_int32), ("lora_r_o", C.c_int32),
+        ("lora_gain_q", C.c_void_p), ("lora_gain_k", C.c_void_p), ("lora_gain_v", C.c_void_p), ("lora_gain_o", C.c_void_p),
     ]
 
 
@@ -134,6 +136,9 @@ def bind(path: str) -> C.CDLL:
     lib.aid_device_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p]
     lib.aid_gemm_nt.restype = C.c_int
     lib.aid_gemm_nt.argtypes = [C.POINTER(AidGemmProblem), C.c_int, C.c_int, C.c_void_p]
+    lib.aid_dora_gain.restype = C.c_int
+    lib.aid_dora_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_int32, C.c_void_p]
     lib.aid_layernorm.restype = C.c_int
     lib.aid_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
                                   C.c_int32, C.c_void_p]

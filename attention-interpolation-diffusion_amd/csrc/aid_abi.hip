@@ -103,6 +103,7 @@ TuneTable g_tune;
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 inline bool dtype16(int d) { return d == AID_DTYPE_F16 || d == AID_DTYPE_BF16; }
 inline bool dtype_ok(int d) { return dtype16(d) || d == AID_DTYPE_F32; }
@@ -125,6 +126,10 @@ int check_problem(const AidGemmProblem& q) {
         if (!q.lr_a || !q.lr_b || q.ln_stats) return AID_ERR_ARG;      // the folded LayerNorm's correction would scale the term too
         if (q.lr_k % 64 || q.lr_k > 512 || q.lr_lda % 8 || q.lr_ldb % 8 || q.lr_lda < q.lr_k || q.lr_ldb < q.lr_k) return AID_ERR_SHAPE;
         if (q.lr_stride_a % 8 || q.lr_stride_b % 8 || !aligned16(q.lr_a) || !aligned16(q.lr_b)) return AID_ERR_SHAPE;
+    }
+    if (q.lr_row_scale) {                                // DoRA gain on the weight rows (ABI v10): part of the low-rank segment
+        if (q.lr_k == 0 || (q.lr_scale_side != 1 && q.lr_scale_side != 2) || !aligned4(q.lr_row_scale)) return AID_ERR_ARG;
+        if (q.trans_rows && q.lr_scale_side != 2) return AID_ERR_ARG;     // the flat value projection: the weight is b
     }
     return AID_OK;
 }
@@ -222,6 +227,9 @@ int check_processor(const AidProcessorArgs& a) {
         if (ranks[i] % 64 || ranks[i] > 512) return AID_ERR_SHAPE;
         if (!ups[i] || !aligned16(ups[i])) return AID_ERR_ARG;
     }
+    const float* gains[4] = {a.lora_gain_q, a.lora_gain_k, a.lora_gain_v, a.lora_gain_o};      // DoRA (ABI v10): only with a rank
+    for (int i = 0; i < 4; ++i)
+        if (gains[i] && (!ranks[i] || !aligned4(gains[i]))) return AID_ERR_ARG;
     if (any) {
         if (a.ln_wq) return AID_ERR_ARG;            // the folded LayerNorm's correction would scale the low-rank term too
         if (a.k_cached && (a.lora_r_k || a.lora_r_v)) return AID_ERR_ARG;     // cached keys must already hold the adapter term
@@ -356,6 +364,7 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
             aid::GemmLRDesc& L = lr.p[i];
             L.a = q.lr_a; L.b = q.lr_b; L.k = q.lr_k; L.lda = q.lr_lda; L.ldb = q.lr_ldb;
             L.stride_a = q.lr_stride_a; L.stride_b = q.lr_stride_b;
+            L.row_scale = q.lr_row_scale; L.side = q.lr_scale_side;
             has_lr = true;
         }
         aid::GemmDesc& d = g.p[i];
@@ -383,6 +392,7 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
             if (q.lr_k > 0)
                 bytes += 2.0 * ((double)q.m * q.lr_k * (q.lr_stride_a || q.batch == 1 ? q.batch : 1) +
                                 (double)q.n * q.lr_k * (q.lr_stride_b || q.batch == 1 ? q.batch : 1));
+            if (q.lr_row_scale) bytes += 4.0 * (q.lr_scale_side == 1 ? q.m : q.n);
         }
     }
     hipError_t e;
@@ -443,6 +453,25 @@ int aid_ln_fold(const void* w, const void* gamma, const void* beta, void* w_fold
     const hipError_t e = aid::ln_fold_launch(w, gamma, beta, w_folded, colsum, shift, rows, c, dtype,
                                              static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_ln_fold");
+}
+
+int aid_dora_gain(const void* w, const void* a_pack, const void* b_pack, const void* magnitude, float* gain, int32_t n_out,
+                  int32_t n_in, int32_t ldw, int32_t rank, int32_t dtype, void* stream) {
+    if (!w || !a_pack || !b_pack || !magnitude || !gain || n_out < 0 || n_in < 1 || rank < 1 || !aligned4(gain)) return AID_ERR_ARG;
+    if (!dtype_ok(dtype)) return AID_ERR_DTYPE;
+    if (n_in % 8 || ldw % 8 || ldw < n_in || rank % 64 || rank > 512) return AID_ERR_SHAPE;
+    if (!aligned16(w) || !aligned16(a_pack) || !aligned16(b_pack) || !aligned16(magnitude)) return AID_ERR_SHAPE;
+    hipError_t e;
+    {
+        // traffic: W, B_pack and the magnitude once, A_pack once per row group (from L2), the gain written
+        const double es = dtype == AID_DTYPE_F32 ? 4.0 : 2.0;
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_dora_gain<%s>", dtype_name(dtype));
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 2.0 * n_out * (double)n_in * (rank + 1),
+                     es * ((double)n_out * n_in + (double)rank * n_in + (double)n_out * rank + n_out) + 4.0 * n_out);
+        e = aid::dora_gain_launch(w, a_pack, b_pack, magnitude, gain, n_out, n_in, ldw, rank, dtype, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_dora_gain");
 }
 
 int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
@@ -623,6 +652,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
     if (a.lora_r_q) {
         pr[0].lr_a = ux; pr[0].lr_lda = cv.rx;
         pr[0].lr_b = a.lora_up_q; pr[0].lr_ldb = a.lora_r_q; pr[0].lr_k = a.lora_r_q;
+        pr[0].lr_row_scale = a.lora_gain_q; pr[0].lr_scale_side = 2;
     }
     {
         char* ue = cross ? uctx : ux;                         // U of the keys' / values' input, its columns, and where k / v start
@@ -631,9 +661,12 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
         if (a.lora_r_k) {
             pr[1].lr_a = ue + ok * es; pr[1].lr_lda = re;
             pr[1].lr_b = a.lora_up_k; pr[1].lr_ldb = a.lora_r_k; pr[1].lr_k = a.lora_r_k;
+            pr[1].lr_row_scale = a.lora_gain_k; pr[1].lr_scale_side = 2;
         }
         if (a.lora_r_v) {
             pr[2].lr_k = a.lora_r_v;
+            pr[2].lr_row_scale = a.lora_gain_v;                 // DoRA: indexed by the weight's rows, n in the flat form, m in the batched
+            pr[2].lr_scale_side = pr[2].trans_rows ? 2 : 1;
             if (pr[2].trans_rows) {                           // flat x Wv^T: LA = U_v (rows like x), LB = B_v
                 pr[2].lr_a = ue + ov * es; pr[2].lr_lda = re;
                 pr[2].lr_b = a.lora_up_v; pr[2].lr_ldb = a.lora_r_v;
@@ -730,6 +763,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
         if (rc != AID_OK) return rc;
         po.lr_a = ws + cv.uo; po.lr_lda = a.lora_r_o;
         po.lr_b = a.lora_up_o; po.lr_ldb = a.lora_r_o; po.lr_k = a.lora_r_o;
+        po.lr_row_scale = a.lora_gain_o; po.lr_scale_side = 2;
     }
     return aid_gemm_nt(&po, 1, a.dtype, stream);
 }

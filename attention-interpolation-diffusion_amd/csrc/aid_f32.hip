@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void aid_gemm_f32_kernel(const GemmGroup g, co
     // ---- epilogue (every option of AidGemmProblem; fp32 needs no intermediate rounding)
     const float* stats = P.ln_stats ? P.ln_stats + 2 * (int64_t)batch * P.stride_stats : nullptr;
     const float* bias = reinterpret_cast<const float*>(P.bias);
-    const float* R = reinterpret_cast<const float*>(P.residual);
+    // (laid out like C, batch stride included — aid_hip.h; the batch offset was missing here until the batched DoRA test met it)
+    const float* R = P.residual ? reinterpret_cast<const float*>(P.residual) + (int64_t)batch * P.stride_c : nullptr;
     const bool vec = !P.trans_rows && !stats && P.n % 4 == 0 &&     // whole 16-byte groups of a row: one store each
                      (reinterpret_cast<uintptr_t>(bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0;
 #pragma unroll
@@ -204,6 +205,18 @@ __global__ __launch_bounds__(256) void aid_gemm_f32_kernel(const GemmGroup g, co
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * gq + e] * P.scale;
+                    // DoRA: gain on the weight rows, before every epilogue step.  (Here, as the accumulators leave their registers:
+                    // all of them scaled at once after the K loops cost the big tile a wave of occupancy.)
+                    if constexpr (std::is_same<LRT, GemmLR>::value) {
+                        const GemmLRDesc& L = lr.p[p];
+                        if (L.row_scale) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * gq + e];
+                            lr_row_scale4(v, L.row_scale, L.side, m, nb, P.n);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] *= P.scale;
+                        }
+                    }
                     if (bias) v += *reinterpret_cast<const f32x4*>(bias + nb);
                     const int64_t off = (int64_t)m * P.ldc + nb;
                     if (R) v += *reinterpret_cast<const f32x4*>(R + off);
@@ -218,6 +231,10 @@ __global__ __launch_bounds__(256) void aid_gemm_f32_kernel(const GemmGroup g, co
                         continue;
                     }
                     float v = acc[i][j][4 * gq + e];
+                    if constexpr (std::is_same<LRT, GemmLR>::value) {
+                        const GemmLRDesc& L = lr.p[p];
+                        if (L.row_scale) v *= L.row_scale[L.side == 1 ? m : n];
+                    }
                     if (stats) {                                   // folded LayerNorm: rstd (x W'^T - mean colsum) + shift
                         if (P.ln_side == 1) v = fmaf(stats[2 * m + 1], fmaf(-stats[2 * m], P.ln_colsum[n], v), P.ln_shift[n]);
                         else                v = fmaf(stats[2 * n + 1], fmaf(-stats[2 * n], P.ln_colsum[m], v), P.ln_shift[m]);

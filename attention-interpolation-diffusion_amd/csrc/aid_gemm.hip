@@ -277,6 +277,11 @@ __global__ __launch_bounds__(GTHREADS) void aid_gemm_nt_kernel(const GemmGroup g
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[in][im][gq * 4 + e];
+                if constexpr (std::is_same<LRT, GemmLR>::value) {      // DoRA: gain on the weight rows, before every epilogue step
+                    // (here, as the accumulators leave their registers: all 64 scaled at once cost 26 VGPRs more)
+                    const GemmLRDesc& L = lr.p[tc.p];
+                    if (L.row_scale) lr_row_scale4(v, L.row_scale, L.side, m, n, P.n);
+                }
                 if (P.ln_stats) ln_fix4(P, P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats, m, n, v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] *= P.scale;
@@ -1473,7 +1478,8 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
 
 // ---- one output tile per workgroup ------------------------------------------------------------------
 // LRT = GemmLR: the low-rank segment rides along (NoLR: none).  mac() ends with no VMEM operation outstanding and the ring released, so
-// the segment is a second set_tile + mac over the LA / LB operands into the same accumulators.
+// the segment is a second set_tile + mac over the LA / LB operands into the same accumulators.  A DoRA gain (GemmLRDesc.row_scale)
+// multiplies them there, in registers, before store_tile — which the ping-pong kernels share — sees them.
 template <typename T, int BM, int BN, int BK, int NS, int WM, int WN, typename LRT>
 __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const GemmGroup g, const LRT lr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1493,6 +1499,10 @@ __global__ __launch_bounds__(WM * WN * 64) void aid_gemm_nt_pipe_kernel(const Ge
             e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
                           reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
             e.mac(0, L.k / BK);
+        }
+        if (L.row_scale) {                                 // DoRA: gain on the weight rows, before every epilogue step
+            mfma_fence(e.acc);
+            lr_row_scale(e.acc, L.row_scale, L.side, tc.m0 + e.wm + e.l31, tc.n0 + e.wn + e.hi * 4, P.m, P.n);
         }
     }
     e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
@@ -1822,6 +1832,7 @@ static void untranspose(GemmGroup& g, GemmLR* lr) {
             L.a = o.b; L.b = o.a;
             L.lda = o.ldb; L.ldb = o.lda;
             L.stride_a = 0; L.stride_b = (int64_t)d.trans_rows * o.lda;
+            L.side = 3 - o.side;                                 // the gain follows the weight operand: columns -> rows
         }
         const int rows = d.trans_rows, frames = d.m / rows;
         GemmDesc o = d;

@@ -41,13 +41,63 @@ struct GemmGroup {                        // passed by value as the kernel argum
 struct GemmLRDesc {
     const void* a;                                    // [m, k] (row stride lda), batch b at a + b * stride_a
     const void* b;                                    // [n, k] (row stride ldb)
-    int32_t k, lda, ldb, reserved;
+    int32_t k, lda, ldb;
+    int32_t side;                                     // row_scale is indexed by m (1) or by n (2)
     int64_t stride_a, stride_b;
+    const float* row_scale;                           // DoRA gain on the weight rows (AidGemmProblem.lr_row_scale); NULL = none
 };
 struct GemmLR {
     GemmLRDesc p[AID_GEMM_MAX_PROBLEMS];
 };
 struct NoLR {};                                       // no low-rank segment
+
+// DoRA gain of a GemmLR problem: the accumulators of a wave (blocks [n block][m block] in the mfma32 result layout: register r of lane
+// (l31, hi) is row m + 32 * (m block), column n + 32 * (n block) + 8 * (r >> 2) + (r & 3), with m / n the lane's first row / column)
+// times gain[column] (side 2) or gain[row] (side 1).  Indices are clamped to the matrix; what lies past it is never stored.
+// Scalar multiplies on purpose (the empty asm keeps hipcc from pairing them, see Engine::store_tile in aid_gemm.hip).
+// the same for the four consecutive columns n .. n + 3 of row m (m inside the matrix) that an epilogue step holds
+template <typename V4>
+__device__ __forceinline__ void lr_row_scale4(V4& v, const float* __restrict__ gain, int side, int m, int n, int N) {
+    const float gm = gain[side == 1 ? m : min(n, N - 1)];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t = v[e] * (side == 1 || e == 0 ? gm : gain[min(n + e, N - 1)]);
+        asm volatile("" : "+v"(t));
+        v[e] = t;
+    }
+}
+template <int NB, int MB, typename ACC>
+__device__ __forceinline__ void lr_row_scale(ACC (&acc)[NB][MB], const float* __restrict__ gain, int side, int m, int n, int M, int N) {
+    if (side == 1) {
+#pragma unroll
+        for (int j = 0; j < MB; ++j) {
+            const float gm = gain[min(m + 32 * j, M - 1)];
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float t = acc[i][j][r] * gm;
+                    asm volatile("" : "+v"(t));
+                    acc[i][j][r] = t;
+                }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float gn = gain[min(n + 32 * i + 8 * gq + e, N - 1)];
+#pragma unroll
+                    for (int j = 0; j < MB; ++j) {
+                        float t = acc[i][j][4 * gq + e] * gn;
+                        asm volatile("" : "+v"(t));
+                        acc[i][j][4 * gq + e] = t;
+                    }
+                }
+    }
+}
 
 // fills g.tile_start (the kernels' block -> problem map) in units of bm x bn tiles and returns the tile count (aid_gemm.hip)
 int fill_tile_start(GemmGroup& g, int bm, int bn);
@@ -138,6 +188,9 @@ hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, 
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);
 hipError_t ln_fold_launch(const void* w, const void* gamma, const void* beta, void* w_folded, float* colsum, float* shift,
                           int rows, int c, int dtype, hipStream_t stream);
+// DoRA row gain (aid_dora.hip): gain[n] = magnitude[n] / ||W[n, :] + (B_pack A_pack)[n, :]||
+hipError_t dora_gain_launch(const void* w, const void* a_pack, const void* b_pack, const void* magnitude, float* gain, int n_out,
+                            int n_in, int ldw, int rank, int dtype, hipStream_t stream);
 bool       layernorm_width_supported(int c);
 
 }  // namespace aid

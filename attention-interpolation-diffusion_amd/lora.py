@@ -12,8 +12,17 @@ the projection's GEMM accumulator (include/aid_hip.h, AidProcessorArgs.lora_* / 
 
 PEFT's forward decision table is mirrored: ``disable_adapters`` -> base only (a merged layer is unmerged first, as PEFT's forward
 does); ``merged`` -> base only (the deltas already sit in the base weight); otherwise every active adapter present in ``lora_A``.
-What the packs cannot express raises NotImplementedError: DoRA, ``lora_bias``, dropout with p > 0 in training mode and the old
+What the packs cannot express raises NotImplementedError: ``lora_bias``, dropout with p > 0 in training mode and the old
 ``LoRACompatibleLinear.lora_layer``.
+
+DoRA (``use_dora[adapter]`` with ``lora_magnitude_vector[adapter].weight`` of shape [out]).  In eval mode PEFT computes
+``g o (x W^T + s B A x) + bias`` with the row gain ``g[n] = magnitude[n] / ||W[n, :] + s (B A)[n, :]||`` (no gradient, no epsilon),
+and re-materialises ``B A`` and the norm on every forward.  The gain depends on weights only: the pack of a DoRA layer also holds
+``gain`` (fp32 [out], ``ops.dora_gain`` — one HIP launch per pack), keyed additionally by the base weight's and the magnitude's
+(data_ptr, _version), and the projection GEMM multiplies its fp32 accumulator by it before the epilogue (AidGemmProblem.lr_row_scale).
+Refused (NotImplementedError naming DoRA): the flag without a magnitude vector; a DoRA adapter active together with any other
+adapter of the layer (PEFT feeds the running result into the next adapter's DoRA term; not restated); a quantised or
+``fan_in_fan_out`` base layer.  There is no CPU fallback for the gain.
 """
 from __future__ import annotations
 
@@ -35,7 +44,8 @@ class LoraPack(NamedTuple):
     a: torch.Tensor          # [R, in]  scaling folded in
     b: torch.Tensor          # [out, R]
     rank: int                # R (a multiple of 64)
-    key: tuple               # what the pack was built from (names, scalings, factor versions, dtype, device)
+    key: tuple               # what the pack was built from (names, scalings, factor versions, dtype, device; DoRA: W and magnitude too)
+    gain: Optional[torch.Tensor] = None      # DoRA: fp32 [out] row gain of the projection's accumulator
 
 
 class LoraArgs(NamedTuple):
@@ -46,6 +56,7 @@ class LoraArgs(NamedTuple):
     up: Tuple[Optional[torch.Tensor], ...]     # B_pack of q, k, v, o
     ranks: Tuple[int, int, int, int]
     key: tuple
+    gains: Tuple[Optional[torch.Tensor], ...] = (None, None, None, None)      # DoRA row gains of q, k, v, o (fp32 [c])
 
 
 def is_lora_layer(mod) -> bool:
@@ -56,6 +67,27 @@ def is_lora_layer(mod) -> bool:
 def _flag(d, name: str) -> bool:
     """PEFT keeps use_dora / lora_bias as {adapter: bool} dicts."""
     return bool(d.get(name, False)) if isinstance(d, dict) else False
+
+
+def dora_magnitude(mod, a: str) -> Optional[torch.Tensor]:
+    """The magnitude vector of adapter ``a`` when it is a DoRA adapter (None for plain LoRA).  Raises NotImplementedError for a DoRA
+    layer the HIP path does not compute."""
+    if not _flag(getattr(mod, "use_dora", {}), a):
+        return None
+    mv = getattr(mod, "lora_magnitude_vector", None)
+    try:
+        mag = mv[a].weight if mv is not None and a in mv else None
+    except (TypeError, AttributeError):
+        mag = None
+    n_out = int(mod.lora_B[a].weight.shape[0])
+    if not torch.is_tensor(mag) or tuple(mag.shape) != (n_out,):
+        raise NotImplementedError(f"DoRA adapter {a!r} without a lora_magnitude_vector of shape [{n_out}]")
+    w = mod.base_layer.weight
+    if getattr(mod, "fan_in_fan_out", False):
+        raise NotImplementedError(f"DoRA adapter {a!r} on a fan_in_fan_out layer")
+    if not torch.is_floating_point(w) or hasattr(w, "quant_state") or tuple(w.shape) != (n_out, int(mod.lora_A[a].weight.shape[1])):
+        raise NotImplementedError(f"DoRA adapter {a!r} on a quantised base layer")
+    return mag
 
 
 def active(mod) -> List[Tuple[str, float]]:
@@ -81,15 +113,17 @@ def active(mod) -> List[Tuple[str, float]]:
     for a in names:
         if a not in mod.lora_A:
             continue
-        if _flag(getattr(mod, "use_dora", {}), a):
-            raise NotImplementedError(f"DoRA adapter {a!r}: the HIP path computes plain LoRA only")
+        dora_magnitude(mod, a)                     # raises for a DoRA adapter that cannot be computed
         if _flag(getattr(mod, "lora_bias", {}), a):
-            raise NotImplementedError(f"adapter {a!r} has lora_bias: the HIP path computes plain LoRA only")
+            raise NotImplementedError(f"adapter {a!r} has lora_bias: the HIP path does not compute it")
         drops = getattr(mod, "lora_dropout", None)
         drop = drops[a] if drops is not None and a in drops else None
         if isinstance(drop, nn.Dropout) and drop.p > 0 and drop.training:
             raise NotImplementedError(f"adapter {a!r}: LoRA dropout p = {drop.p} in training mode (call .eval())")
         out.append((a, float(mod.scaling[a])))
+    if len(out) > 1 and any(_flag(getattr(mod, "use_dora", {}), a) for a, _ in out):
+        raise NotImplementedError("a DoRA adapter active together with another adapter of the layer (" +
+                                  ", ".join(repr(a) for a, _ in out) + "): PEFT chains them through the running result")
     return out
 
 
@@ -102,11 +136,15 @@ def _tkey(t: torch.Tensor) -> tuple:
 
 
 def pack(mod, dtype: torch.dtype, device: torch.device) -> Optional[LoraPack]:
-    """The (A_pack, B_pack) of ``mod``'s active adapters in ``dtype`` (cached), or None without any."""
+    """The (A_pack, B_pack) of ``mod``'s active adapters in ``dtype`` (cached), or None without any.  A DoRA layer's pack also holds
+    its row gain."""
     acts = active(mod)
     if not acts:
         return None
     key = (tuple(acts), tuple(_tkey(mod.lora_A[a].weight) + _tkey(mod.lora_B[a].weight) for a, _ in acts), dtype, str(device))
+    mag = dora_magnitude(mod, acts[0][0])          # a DoRA adapter is the only active one (active())
+    if mag is not None:
+        key += (_tkey(mod.base_layer.weight), _tkey(mag))
     ent = _PACK_CACHE.get(mod)
     if ent is not None and ent[0] == key:
         return ent[1]
@@ -128,7 +166,11 @@ def pack(mod, dtype: torch.dtype, device: torch.device) -> Optional[LoraPack]:
             a_pack[row:row + r] = (wa.detach().to(device=device, dtype=torch.float32) * s).to(dtype)
             b_pack[:, row:row + r] = wb.detach().to(device=device, dtype=dtype)
             row += r
-    p = LoraPack(a_pack, b_pack, rank, key)
+        gain = None
+        if mag is not None:                        # DoRA: gain = magnitude / ||W + s B A||_row, from the numbers the GEMM multiplies
+            from . import ops
+            gain = ops.dora_gain(mod.base_layer.weight.detach(), a_pack, b_pack, mag.detach().to(device=device, dtype=dtype).contiguous())
+    p = LoraPack(a_pack, b_pack, rank, key, gain)
     _PACK_CACHE[mod] = (key, p)
     return p
 
@@ -167,7 +209,8 @@ def args(attn, dtype: torch.dtype, device: torch.device, cross: bool, kv: bool =
         down_ctx = torch.cat(ctx_parts, 0).contiguous() if ctx_parts else None
     from . import processors
     processors._CACHE_GEN[0] += 1
-    la = LoraArgs(down_x, down_ctx, None if po is None else po.a, tuple(None if p is None else p.b for p in packs), ranks, key)
+    la = LoraArgs(down_x, down_ctx, None if po is None else po.a, tuple(None if p is None else p.b for p in packs), ranks, key,
+                  tuple(None if p is None else p.gain for p in packs))
     _ARGS_CACHE[attn] = (key, la)
     return la
 

@@ -270,13 +270,21 @@ def gemm_nt(problems: Sequence[dict]) -> None:
             q.ln_stats, q.ln_colsum, q.ln_shift = p["ln_stats"].data_ptr(), p["ln_colsum"].data_ptr(), p["ln_shift"].data_ptr()
             q.ln_side, q.stride_stats = int(p["ln_side"]), int(p.get("stride_stats", 0))
         lr = p.get("lr")
-        if lr is not None:      # low-rank second K segment: dict(a=LA [m, k], b=LB [n, k], k=, lda=, ldb=[, stride_a=, stride_b=])
+        if lr is not None:      # low-rank second K segment: dict(a=LA [m, k], b=LB [n, k], k=, lda=, ldb=[, stride_a=, stride_b=]
+            #                     [, row_scale=fp32 gain of the weight rows (DoRA), scale_side=2 (indexed by n, default) | 1 (by m)])
             _require_gpu(lr["a"], lr["b"])
             if _dtype_code(lr["a"]) != dt or _dtype_code(lr["b"]) != dt:
                 raise TypeError("the low-rank operands must have the GEMM's dtype")
             q.lr_a, q.lr_b = lr["a"].data_ptr(), lr["b"].data_ptr()
             q.lr_k, q.lr_lda, q.lr_ldb = int(lr["k"]), int(lr["lda"]), int(lr["ldb"])
             q.lr_stride_a, q.lr_stride_b = int(lr.get("stride_a", 0)), int(lr.get("stride_b", 0))
+            rs = lr.get("row_scale")
+            if rs is not None:
+                _require_gpu(rs)
+                side = int(lr.get("scale_side", 2))
+                if rs.dtype != torch.float32 or rs.stride(-1) != 1 or rs.numel() != (q.m if side == 1 else q.n):
+                    raise TypeError("row_scale is a float32 vector with one entry per weight row (n for scale_side 2, m for 1)")
+                q.lr_row_scale, q.lr_scale_side = rs.data_ptr(), side
     with _on(problems[0]["a"].device):
         _lib.check(lib.aid_gemm_nt(arr, n, dt, _stream()), "aid_gemm_nt")
 
@@ -348,20 +356,42 @@ def ln_fold(w: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch
     return wf, cs, sh
 
 
+def dora_gain(w: torch.Tensor, a_pack: torch.Tensor, b_pack: torch.Tensor, magnitude: torch.Tensor) -> torch.Tensor:
+    """Row gain of a DoRA adapter (``aid_dora_gain``): ``magnitude / ||W + B_pack A_pack||_row`` as float32 [out].  ``w`` [out, in]
+    (rows may be strided), ``a_pack`` [R, in] with the scaling folded in and ``b_pack`` [out, R] as ``lora.pack`` builds them,
+    ``magnitude`` [out]; all of one dtype (float16 / bfloat16 / float32)."""
+    dev = _require_gpu(w, a_pack, b_pack, magnitude)
+    dt = _dtype_code(w)
+    if any(t_.dtype != w.dtype for t_ in (a_pack, b_pack, magnitude)):
+        raise TypeError("w, a_pack, b_pack and magnitude must share one dtype")
+    n_out, n_in = w.shape
+    rank = a_pack.shape[0]
+    if w.ndim != 2 or w.stride(1) != 1 or tuple(a_pack.shape) != (rank, n_in) or tuple(b_pack.shape) != (n_out, rank) \
+            or magnitude.numel() != n_out or not (a_pack.is_contiguous() and b_pack.is_contiguous() and magnitude.is_contiguous()):
+        raise ValueError("dora_gain takes w [out, in], a_pack [R, in], b_pack [out, R], magnitude [out] (packs and magnitude contiguous)")
+    gain = torch.empty(n_out, dtype=torch.float32, device=w.device)
+    with _on(dev):
+        _lib.check(_lib.load().aid_dora_gain(w.data_ptr(), a_pack.data_ptr(), b_pack.data_ptr(), magnitude.data_ptr(), gain.data_ptr(),
+                                             n_out, n_in, w.stride(0) if n_out > 1 else n_in, rank, dt, _stream()), "aid_dora_gain")
+    return gain
+
+
 def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: int = 0,
-               lora_k: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-               lora_v: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               lora_k: Optional[Tuple[torch.Tensor, ...]] = None,
+               lora_v: Optional[Tuple[torch.Tensor, ...]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """k = e @ wk.T  [F, L, C]  and  V^T = wv @ e^T  [F, C, Lp]  (Lp = L rounded up to 8) in one launch.
     ``extra_rows``: allocate that many more (uninitialised) frame rows behind the F projected ones — room for the
     end-point frames' keys / values a rank receives from their owners (dist.EndpointExchange).
-    ``lora_k`` / ``lora_v`` = (A_pack, B_pack) (lora.pack): the adapters' terms are added in the same accumulators; e is projected
-    down once, U = e [A_k; A_v]^T, in one launch before."""
+    ``lora_k`` / ``lora_v`` = (A_pack, B_pack[, gain]) (lora.pack): the adapters' terms are added in the same accumulators; e is
+    projected down once, U = e [A_k; A_v]^T, in one launch before.  ``gain`` (DoRA, fp32 [C] or None) multiplies the accumulator."""
     f, l, cc = e.shape
     c = wk.shape[0]
     lp = (l + 7) // 8 * 8
     k = torch.empty(f + extra_rows, l, c, dtype=e.dtype, device=e.device)
     vt = torch.empty(f + extra_rows, c, lp, dtype=e.dtype, device=e.device)
     u = None
+    gk = lora_k[2] if lora_k is not None and len(lora_k) > 2 else None
+    gv = lora_v[2] if lora_v is not None and len(lora_v) > 2 else None
     rk = lora_k[0].shape[0] if lora_k is not None else 0
     rv = lora_v[0].shape[0] if lora_v is not None else 0
     if rk + rv:
@@ -371,15 +401,15 @@ def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: 
     if l % 8 == 0:          # flat value projection, transposed epilogue (tile count of the key projection: whole CU rounds)
         pv = dict(a=e, b=wv, c=vt, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=lp, stride_c=c * lp, trans_rows=l)
         if rv:
-            pv["lr"] = dict(a=u[:, rk:], b=lora_v[1], k=rv, lda=rk + rv, ldb=rv)
+            pv["lr"] = dict(a=u[:, rk:], b=lora_v[1], k=rv, lda=rk + rv, ldb=rv, row_scale=gv, scale_side=2)
     else:                   # V^T[f] = Wv E_f^T, one batch entry per frame.  Pad columns l .. round_up(l, 4) of V^T are written with
         #                     zeros (aid_hip.h); round_up(l, 4) .. lp are not written, and the attention kernels do not read their values
         pv = dict(a=wv, b=e, c=vt, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=lp, batch=f, stride_a=0, stride_b=l * cc, stride_c=c * lp)
         if rv:
-            pv["lr"] = dict(a=lora_v[1], b=u[:, rk:], k=rv, lda=rv, ldb=rk + rv, stride_b=l * (rk + rv))
+            pv["lr"] = dict(a=lora_v[1], b=u[:, rk:], k=rv, lda=rv, ldb=rk + rv, stride_b=l * (rk + rv), row_scale=gv, scale_side=1)
     pk = dict(a=e, b=wk, c=k, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c)
     if rk:
-        pk["lr"] = dict(a=u, b=lora_k[1], k=rk, lda=rk + rv, ldb=rk)
+        pk["lr"] = dict(a=u, b=lora_k[1], k=rk, lda=rk + rv, ldb=rk, row_scale=gk, scale_side=2)
     gemm_nt([pk, pv])
     return k, vt
 
@@ -518,7 +548,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``score_bias_layout``); the library refuses it together with ``fused`` or ``ip`` (the reference fails there, aid_hip.h).
     ``lora``: unmerged LoRA adapters of the four projections (``lora.LoraArgs``, AidProcessorArgs.lora_*): each projection with a
     rank computes  in W^T + round(in A_pack^T) B_pack^T  in its GEMM accumulator; refused with ``ln_folded`` and, on k / v, with
-    ``kv_cached`` (the cached keys must already hold the adapter term)."""
+    ``kv_cached`` (the cached keys must already hold the adapter term).  ``lora.gains`` (DoRA, AidProcessorArgs.lora_gain_*): the
+    fp32 row gain of each projection's adapter, or None."""
     lib = _lib.load()
     ipt = ip or {}
     dev = _require_gpu(x, ctx, wq, wk, wv, wo, bo, coef, ctx_map, out, residual, attn_bias, *(ln[:2] if ln else ()),
@@ -614,6 +645,13 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
         a.lora_down_x, a.lora_down_ctx, a.lora_down_o = _ptr(lora.down_x), _ptr(lora.down_ctx), _ptr(lora.down_o)
         a.lora_up_q, a.lora_up_k, a.lora_up_v, a.lora_up_o = (_ptr(t_) for t_ in lora.up)
         a.lora_r_q, a.lora_r_k, a.lora_r_v, a.lora_r_o = lora.ranks
+        gains = tuple(getattr(lora, "gains", None) or (None,) * 4)
+        for t_, r_ in zip(gains, lora.ranks):
+            if t_ is not None:
+                _require_gpu(t_)
+                if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() != c or not r_:
+                    raise ValueError("DoRA gains are contiguous float32 [C] tensors of projections that have a rank")
+        a.lora_gain_q, a.lora_gain_k, a.lora_gain_v, a.lora_gain_o = (_ptr(t_) for t_ in gains)
     a.cu_share = current_cu_share()
     nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):

@@ -373,7 +373,8 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
     hit = per.get(key)
     if hit is None:
         _CACHE_GEN[0] += 1
-        kw = {} if lk is None and lv is None else dict(lora_k=None if lk is None else lk[:2], lora_v=None if lv is None else lv[:2])
+        kw = {} if lk is None and lv is None else dict(lora_k=None if lk is None else (lk.a, lk.b, lk.gain),
+                                                       lora_v=None if lv is None else (lv.a, lv.b, lv.gain))
         k, vt = ops.project_kv(ctx, wk, wv, **kw)
         for old in [kk for kk in per if kk[0][0] == key[0][0] and kk[3:6] == key[3:6]]:
             per.pop(old, None)            # the same tensor at an older version (or with replaced weights)

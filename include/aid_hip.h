@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define AID_ABI_VERSION 9
+#define AID_ABI_VERSION 10
 
 /* element types of activations / weights (accumulation is always fp32) */
 #define AID_DTYPE_F16  0
@@ -127,12 +127,36 @@ typedef struct AidGemmProblem {
     int32_t      lr_k;
     int32_t      lr_lda;
     int32_t      lr_ldb;
-    int32_t      reserved1;
+    int32_t      lr_scale_side;  /* ABI v10: which dimension lr_row_scale is indexed by (below); ignored without it */
     int64_t      lr_stride_a;
     int64_t      lr_stride_b;
+    /* ABI v10 — gain on the weight rows of a problem with a low-rank segment (NULL: none): a DoRA adapter,                      */
+    /*     C = epilogue( scale * gain o (A B^T + LA LB^T) + bias ... )                                                           */
+    /* The fp32 accumulator is multiplied by the fp32 gain after the low-rank segment and before every epilogue step (the scale,  */
+    /* bias, rounding, residual and the transposed-per-frame store).  lr_scale_side 2: the weight operand is b, the gain is       */
+    /* indexed by column n and has n entries; 1: the weight operand is a (the batched V^T[f] = Wv E_f^T form), the gain is        */
+    /* indexed by row m and has m entries.  One gain for all batches (no stride).  With trans_rows the side is 2 (the gain is     */
+    /* applied before the transposition).  AID_ERR_ARG: with lr_k == 0, a side other than 1 / 2, a base that is not 4-byte        */
+    /* aligned; with ln_stats the segment itself is refused.  aid_dora_gain computes the gain of a DoRA layer.                    */
+    const float* lr_row_scale;
 } AidGemmProblem;
 
 int aid_gemm_nt(const AidGemmProblem* problems /* host */, int n_problems, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * ABI v10.  Row gain of a DoRA adapter (PEFT's DoRA layers in eval mode; weights only, so once per adapter pack):
+ *   gain[n] = magnitude[n] / || W[n, :] + (B_pack A_pack)[n, :] ||_2          (no epsilon, like PEFT)
+ *   w [n_out, n_in] (row stride ldw) the base weight, a_pack [rank, n_in] the adapter's lora_A rows with its scaling folded
+ *   in, b_pack [n_out, rank] its lora_B (both contiguous, zero-padded to `rank`: the operands of the low-rank segment),
+ *   magnitude [n_out] — all in the storage dtype (f16 / bf16 / f32); gain [n_out] fp32.  The row W + B A is formed and squared
+ *   in fp32 and never written.  With AidGemmProblem.lr_row_scale = gain the projection computes PEFT's DoRA forward
+ *   gain o (x W^T + s B A x) + bias.
+ * Requirements: n_in % 8 == 0, ldw % 8 == 0, ldw >= n_in, rank % 64 == 0, 64 <= rank <= 512, w / a_pack / b_pack / magnitude
+ * 16-byte aligned (AID_ERR_SHAPE), gain 4-byte aligned.  Reads exactly the [n_out, n_in] / [rank, n_in] / [n_out, rank] / [n_out]
+ * elements, writes exactly n_out floats.  One launch, no allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------- */
+int aid_dora_gain(const void* w, const void* a_pack, const void* b_pack, const void* magnitude, float* gain, int32_t n_out,
+                  int32_t n_in, int32_t ldw, int32_t rank, int32_t dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * LayerNorm over the last dimension: y[r, :] = (x[r, :] - mean_r) * rsqrt(var_r + eps) * gamma + beta
@@ -332,6 +356,13 @@ typedef struct AidProcessorArgs {
     int32_t      lora_r_k;
     int32_t      lora_r_v;
     int32_t      lora_r_o;
+    /* ---- ABI v10: DoRA.  lora_gain_p (fp32 [c], NULL: none; only with lora_r_p > 0, else AID_ERR_ARG) is the row gain of      */
+    /* projection p's adapter (aid_dora_gain): the projection computes  gain_p o (in W_p^T + U_p B_p^T)  (AidGemmProblem.         */
+    /* lr_row_scale, with the side of the form the call plans for that projection).  The down projections U are unchanged.        */
+    const float* lora_gain_q;
+    const float* lora_gain_k;
+    const float* lora_gain_v;
+    const float* lora_gain_o;
 } AidProcessorArgs;
 
 size_t aid_processor_workspace_bytes(const AidProcessorArgs* args /* host */);
