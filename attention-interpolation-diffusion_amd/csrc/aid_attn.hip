@@ -1292,11 +1292,17 @@ AttnPlan plan_attn(const AidAttnArgs& a) {
     //   default: calls it can run ALONE (several segments per frame: multiples of 512 keys), fused OUTER and INNER from 1024 keys, PLAIN
     //   and pure OUTER from 2048 — same-process A/B, us: S = 4096 plain 648 -> 588, outer 1160 -> 1078, inner 915 -> 860; S = 1024 outer
     //   163.5 -> 161.1, inner 130.6 -> 135.3, plain 93 -> 110 (a 16-tile stream on one workgroup per CU; profiles/r03_attn_notes.txt).
+    //   PLAIN from 1024 keys too WHEN THE PERSISTENT WALK APPLIES (attn_pp_persistent: more items than CUs, whole 8-tile trips): with the
+    //   item boundary of round 7 the S = 1024 launch of the SDXL stack runs 81.8 us there against 90.4 on aid_attn<…,plain,nw4>, same
+    //   process, spread 1 us (profiles/r07_attn_pp_boundary.md).  One item per workgroup stays slower at 16 tiles: a call with few
+    //   items stays on the program-order kernel.  Measured at l = 1024 only; the key counts between (1536: three trips) follow the
+    //   same per-item model but have not been timed against the program-order kernel.
     //   ATTN_V2 = 0 never; 1 wherever supported (tests) — a call it cannot run alone is then split: single-segment frames on it, the
     //   others on aid_attn_kernel in a second launch.
     // (a call with several segments per frame: segments of whole 8-tile trips; INNER: k2 / vt2 present)
     const bool alone = a.mode == AID_MODE_PLAIN || (a.l % 512 == 0 && (a.mode == AID_MODE_OUTER || (a.k2 && a.vt2)));
-    const bool dflt = a.l >= ((a.mode == AID_MODE_PLAIN || (a.mode == AID_MODE_OUTER && !a.fused)) ? 2048 : 1024);
+    const bool dflt = a.l >= ((a.mode == AID_MODE_PLAIN || (a.mode == AID_MODE_OUTER && !a.fused)) ? 2048 : 1024) ||
+                      (a.mode == AID_MODE_PLAIN && a.l >= 1024 && attn_pp_persistent(a, true, nullptr));
     if (!a.bias && attn_pp_supported(a) && (alone || pl.n_single > 0) &&   // (a score bias: aid_attn_kernel's BIAS instantiation)
         (v2 == 1 || (v2 < 0 && alone && dflt))) {
         const char* const kind = a.mode == AID_MODE_PLAIN ? "" : a.mode == AID_MODE_OUTER ? ",outer" : ",inner";

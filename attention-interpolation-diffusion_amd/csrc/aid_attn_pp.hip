@@ -29,6 +29,12 @@
 // persistent walk for every mode, staged stores; bf16 row sums on the matrix pipe + exponent-bit test, no padding in the loop,
 // straight-line fast path: S = 4096 plain 524 - 562 us by box, fused outer 880 - 965, S = 1024 fused outer 132 - 143.
 // aid_attn_fwd's default rule: fused OUTER / INNER from 1024 keys, everything else from 2048.
+// Round 7 (profiles/r07_attn_pp_boundary.md): the item boundary of a persistent workgroup, stamped (ablation bit 256).  The counted wait
+// is NOT where it goes — finish() 1800 cycles, walk + plan + Q request 2200 (OUTER 2600 / 3200 - 3600), the `fresh` V(0) 1600, and all of it
+// TWICE: group 0 did it with group 1 parked at the barrier, then group 1 with group 0 parked (11400 cycles per boundary, plain).  Now
+// group 1 does its boundary work in front of the barrier behind its last M slot, beside group 0's (`defer`); the walk hands plan() the
+// item's (head, frame, q block) instead of an id to divide again; the per-frame records (coefficient, frame scale, key-row map) are
+// scalar loads — as vector loads behind the kernel's stores each was drained by vmcnt(0), once per item in every OUTER / INNER launch.
 #include <type_traits>
 
 #include "aid_common.hpp"
@@ -75,6 +81,20 @@ __device__ __forceinline__ float dot2_ones<f16>(uint32_t w, float acc) {
     one[0] = (_Float16)1.0f; one[1] = (_Float16)1.0f;
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, w), one, acc, false);
 }
+
+// One per-frame record (coefficient, frame scale, key-row map) at a wave-uniform index, read through the CONSTANT address space: a
+// scalar load.  As a plain global load it is a VECTOR load behind the kernel's stores (the compiler cannot prove the memory unwritten)
+// and its use waits vmcnt(0) — in the middle of an item boundary that drains the DMA ring.  The call's inputs are never written here.
+template <typename V>
+__device__ __forceinline__ V ld_uniform(const V* ptr, int i) {
+    return reinterpret_cast<const __attribute__((address_space(4))) V*>(reinterpret_cast<uintptr_t>(ptr))[i];
+}
+
+#ifdef AID_ABLATIONS
+#define PP_LDU(ptr, i) ((p.abl & 512) ? (ptr)[i] : ld_uniform(ptr, i))     // 512: the records as plain (vector) loads, each drained by vmcnt(0)
+#else
+#define PP_LDU(ptr, i) ld_uniform(ptr, i)
+#endif
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -138,35 +158,47 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         pb = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
         npx = q + (xcd < r ? 1 : 0);
     }
-    // this workgroup's j-th item as a logical id of the [head][frame][q block] order (>= n_items: none)
-    auto item_lid = [&](int j) __attribute__((always_inline)) {
+    // this workgroup's j-th item as (head, frame, q block) of the [head][frame][q block] order (ok = false: none).  Everything
+    // that does not depend on j is formed once here, and the item comes out in the components plan() needs — the walk used to return the
+    // logical id, which plan() took apart again: a dozen emulated integer divisions per item on the serial path of an item boundary
+    // (profiles/r07_attn_pp_boundary.md); two are left (t by npx, the pair by nqb).
+    int hc = 0, hr = 0, c1 = 0, p2 = 0, nlx = 0;                // persistent walk: heavy items of this workgroup, remainder, levelling
+    if (p.persist) {
+        const int nhx = npx * nhf;
+        nlx = npx * (a.n_frames - nhf);
+        const int hq = nhx / WX;
+        hr = nhx % WX;
+        hc = hq + (wx < hr ? 1 : 0);                            // heavy items of this workgroup
+        const int ndef = hr > 0 ? WX - hr : 0;                  // workgroups one heavy item short
+        p2 = min(nlx, p.hv_units * ndef);                       // light items [0, p2) level them
+        c1 = (hr > 0 && wx >= hr) ? max(min(p.hv_units * (wx - hr + 1), p2) - p.hv_units * (wx - hr), 0) : 0;
+    }
+    struct Item { int h, fr, qb; bool ok; };
+    auto item_at = [&](int j) __attribute__((always_inline)) -> Item {
+        const Item none = {0, 0, 0, false};
         if (!p.persist) {
-            if (j != 0) return n_items;
-            return hf ? heavy_first((int)blockIdx.x, n_items, n_heavy * p.nqb, a.n_frames * p.nqb) : xcd_remap((int)blockIdx.x, n_items);
+            if (j != 0) return none;
+            const int lid = hf ? heavy_first((int)blockIdx.x, n_items, n_heavy * p.nqb, a.n_frames * p.nqb) : xcd_remap((int)blockIdx.x, n_items);
+            if (lid >= n_items) return none;
+            return Item{lid / (p.nqb * a.n_frames), (lid / p.nqb) % a.n_frames, lid % p.nqb, true};
         }
-        const int nhx = npx * nhf, nlx = npx * (a.n_frames - nhf);
-        const int hq = nhx / WX, hr = nhx % WX;
-        const int hc = hq + (wx < hr ? 1 : 0);                  // heavy items of this workgroup
         int t, fr;
         if (j < hc) {
             t = wx + j * WX;                                    // t-th heavy item of the XCD, order [frame][pair]
             fr = p.hv_lo + t / npx;
         } else {
             const int jj = j - hc;
-            const int ndef = hr > 0 ? WX - hr : 0;              // workgroups one heavy item short
-            const int p2 = min(nlx, p.hv_units * ndef);         // light items [0, p2) level them
-            const int c1 = (hr > 0 && wx >= hr) ? max(min(p.hv_units * (wx - hr + 1), p2) - p.hv_units * (wx - hr), 0) : 0;
             if (jj < c1) {
                 t = p.hv_units * (wx - hr) + jj;
             } else {
                 t = p2 + wx + (jj - c1) * WX;
-                if (t >= nlx) return n_items;
+                if (t >= nlx) return none;
             }
             const int fi = t / npx;                             // t-th light item of the XCD
             fr = fi < p.hv_lo ? fi : fi + nhf;
         }
         const int pi = pb + t % npx;
-        return ((pi / p.nqb) * a.n_frames + fr) * p.nqb + pi % p.nqb;
+        return Item{pi / p.nqb, fr, pi % p.nqb, true};
     };
     // Key segments of a frame (the same decisions aid_attn_kernel takes, on the same device coefficients):
     //   single  — PLAIN call, negative coefficient (PLAIN rider of a batched-CFG call), fused END-POINT frame: own keys only.
@@ -184,16 +216,15 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     int N_park = -1, N_swap = -1;
     float N_wb = 0.f, N_we = 1.f;
     bool N_skip = false;
-    auto plan = [&](int lid) __attribute__((always_inline)) {
-        const int qb = lid % p.nqb;
-        N_fr = (lid / p.nqb) % a.n_frames;
-        N_h = lid / (p.nqb * a.n_frames);
-        N_q0 = (qb * 8 + wave) * 32;
-        const int kvf = a.kv_map ? a.kv_map[N_fr] : N_fr;
+    auto plan = [&](const Item it) __attribute__((always_inline)) {
+        N_fr = it.fr;
+        N_h = it.h;
+        N_q0 = (it.qb * 8 + wave) * 32;
+        const int kvf = a.kv_map ? PP_LDU(a.kv_map, N_fr) : N_fr;
         int seg0 = kvf, seg1 = 0;
         N_nseg = 1; N_t2 = 0; N_park = -1; N_swap = -1; N_wb = 0.f; N_we = 1.f; N_skip = false;
         if (MODE != AID_MODE_PLAIN) {
-            const float cf = a.coef[N_fr];
+            const float cf = PP_LDU(a.coef, N_fr);
             const bool single = cf < 0.f || (a.fused && ((cf == 0.f && kvf == row_b) || (cf == 1.f && kvf == row_e)));
             if (!single) {
                 N_skip = !p.multi;
@@ -230,8 +261,8 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         NT = nseg * nt;
     };
     {
-        const int first = item_lid(0);
-        if (first >= n_items) return;                           // a persistent workgroup the deal left empty (fewer items than the balance needs)
+        const Item first = item_at(0);
+        if (!first.ok) return;                                  // a persistent workgroup the deal left empty (fewer items than the balance needs)
         plan(first);
     }
     if (N_skip) return;                                         // (split launches are never persistent)
@@ -369,8 +400,31 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         }
     };
 #define PP_STAMP(i) stamp(i)
+    // 256: timeline of ONE item boundary per wave (behind the workgroup's second item; the item after it has a successor from four items per
+    // workgroup on): shader cycles since the barrier behind the finished item's last M slot of [finish() done | plan + Q request done |
+    // V(0) done, the barrier behind it passed | ... V(3) ... ].  The item runs and stores as usual; lane 0 of every wave writes the eleven
+    // stamps behind a two-word mark over the first row of the item the boundary led INTO when the kernel ends (tools/dev/pp_timeline.py).
+    // With `defer` the second group's barrier behind its last M slot lies behind its finish() and plan + Q request: ITS origin is the end
+    // of that M slot, its first two stamps are taken in front of that barrier and "plan + Q request done" includes the wait at it — the
+    // group's row is not comparable stamp for stamp with a timeline of the kernel before round 7; compare the V(1) ... V(3) columns.
+    long long bt0 = 0;
+    uint32_t bt[11];
+    for (int i = 0; i < 11; ++i) bt[i] = 0;
+    int64_t boff = -1;
+    bool barm = false;
+    auto bstamp = [&](int which) __attribute__((always_inline)) {
+        if (barm) {
+            __builtin_amdgcn_sched_barrier(0);
+            const long long now = clock64();
+            if (which == 0) bt0 = now;
+            bt[which] = (uint32_t)(now - bt0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+#define PP_BSTAMP(i) bstamp(i)
 #else
 #define PP_STAMP(i)
+#define PP_BSTAMP(i) do {} while (0)
 #endif
 
     // MFMA results and the VALU code that reads them.  The hazard recogniser does not see across the slots' barriers / branches
@@ -448,6 +502,9 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     // the PV MFMAs; 16 v_dot2c + 2 v_mov + 2 v_add less here: -0.4 ... -4 % per launch, profiles/r04_attn_notes.txt table 5).
     // (The requests stay HERE: issued from the M slot they cost 3 - 18 %, table 4.)
     constexpr int LEAD = 6;
+    // (The counted wait behind an item boundary stays vmcnt(6) although the finished item's stores and the next Q request then sit in
+    //  front of tile t + 6: the walk and plan() lie between them and the wait, and everything has long landed — a lax count, exact per
+    //  path, measured no difference in any launch: profiles/r07_attn_pp_boundary.md.)
     auto vslot = [&](int t, bool first) __attribute__((always_inline)) {
         // The DMA stream never stops: behind the workgroup's last item it wraps into that item's first segment again (valid memory,
         // nobody reads those stages), so the slot has no "is there a tile t + LEAD" branch and ONE counted wait — the tail logic cost
@@ -607,7 +664,7 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         const float lown = get_l();
         const float inv = w_e / (lown + other_half(lown));      // (w_e = 1 unless this frame mixes two sides)
         if (q0 >= a.s) return;                                  // (wave-uniform: a wave past the last row)
-        const float osc = a.out_scale * (a.frame_scale ? a.frame_scale[fr] : 1.f);
+        const float osc = a.out_scale * (a.frame_scale ? PP_LDU(a.frame_scale, fr) : 1.f);
         if (MODE == AID_MODE_OUTER) {
             // (the OUTER instantiation sits at 250 of 256 registers with the parked state: it keeps the 8-byte row-per-lane stores — its
             //  items are two or three key segments long, the store tail is <= 3 % of an item)
@@ -696,14 +753,24 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     // Items: for (;;) { plan the next item, request its Q rows; walk this item's tiles; finish it; adopt the next }.  Every tile t of an
     // item gets V(t) and M(t + 1); behind the LAST tile "t + 1" is tile 0 of the next item (its Q fragments are read back from LDS
     // right before that M slot) or, for the workgroup's last item, stale ring bytes whose scores nobody reads.
+    // The two groups at an item boundary.  Group 0 passes the barrier behind its last M slot and does the boundary work — finish(), the walk
+    // and plan() of the item after next, its Q request, the `fresh` first V slot: about 5500 cycles where a steady interval is 1100 — with
+    // group 1 (one M slot of work) waiting at the next barrier; then group 1 did the same with group 0 waiting: the boundary was paid TWICE,
+    // back to back (measured 11400 cycles per boundary, profiles/r07_attn_pp_boundary.md).  None of that work touches the ring (the output
+    // staging and the Q rows are the wave's own 4 KB) and the barrier is no vector-memory operation, so group 1 of a persistent workgroup
+    // runs its boundary work in FRONT of the barrier behind its last M slot, beside group 0's: same barriers per item, same order of every
+    // wave's memory operations, V(0) still between the same two barriers.
+    const bool defer = p.persist && grp == 1;
 #pragma nounroll
     for (int j = 0;; ++j) {
-        const int vbn = item_lid(j + 1);
-        has_next = vbn < n_items;
+        const Item nxt = item_at(j + 1);
+        has_next = nxt.ok;
         if (has_next) {
-            plan(vbn);
+            plan(nxt);
             dma_q_next();
         }
+        if (defer && j > 0) slot_barrier();                     // the barrier behind the previous item's last M slot
+        PP_BSTAMP(2);
         // One pass per key segment (`nounroll`: one copy of the body); inside, eight tiles per trip: t & 7 — the ring stage of every
         // DMA and fragment read — is a compile-time constant in each copy (segments of a multi-segment frame, and every item of a
         // persistent launch, are whole trips).
@@ -731,17 +798,33 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
                         asm volatile("" : "+v"(cneg));
                     }
                     PP_STAMP(0);
+                    if (i < 4) PP_BSTAMP(3 + 2 * i);
                     slot_barrier();
                     PP_STAMP(1);
+                    if (i < 4) PP_BSTAMP(4 + 2 * i);
+#ifdef AID_ABLATIONS
+                    if (i == 3 && barm) {                       // (the boundary's item is adopted: its first row takes the stamps)
+                        barm = false;
+                        if (q0 < a.s) boff = (int64_t)fr * a.o_fs + (int64_t)q0 * a.ldo + h * D;
+                    }
+#endif
                     mslot(i, (i + 2) & 7);
                     tie();
                     PP_STAMP(2);
-                    slot_barrier();
+                    if (!(i == 7 && defer && t == NT - 1)) slot_barrier();      // (the second group: behind the boundary work, see `defer`)
                 }
             }
         }
+#ifdef AID_ABLATIONS
+        barm = (p.abl & 256) && j == 1 && has_next;
+#endif
+        PP_BSTAMP(0);
         finish();
-        if (!has_next) break;
+        PP_BSTAMP(1);
+        if (!has_next) {
+            if (defer) slot_barrier();
+            break;
+        }
         // the next item: its S(0) is in `sc`; everything else starts over
         fresh = true;
         set_l(0.f);
@@ -757,6 +840,13 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         dseg = 0;                                               // the DMA stream is LEAD tiles into this item's first segment already
     }
     wait_vm<0>();                            // (the wrapped requests behind the last item: nobody reads them)
+#ifdef AID_ABLATIONS
+    if ((p.abl & 256) && boff >= 0 && lane == 0) {
+        uint32_t* dbg = reinterpret_cast<uint32_t*>(reinterpret_cast<T*>(a.out) + boff);
+        dbg[0] = 0x50504254u; dbg[1] = 0x4c494e45u;             // the mark
+        for (int i = 0; i < 11; ++i) dbg[2 + i] = bt[i];
+    }
+#endif
     if (grp == 0) slot_barrier();                               // both groups pass the same number of barriers
 }
 
@@ -773,8 +863,34 @@ bool attn_pp_supported(const AidAttnArgs& a) {
     const int64_t qb = (int64_t)a.n_frames * a.q_fs * 2, ob = (int64_t)a.n_frames * a.o_fs * 2;
     const uintptr_t al = reinterpret_cast<uintptr_t>(a.k) | reinterpret_cast<uintptr_t>(a.vt) | reinterpret_cast<uintptr_t>(a.k2) |
                          reinterpret_cast<uintptr_t>(a.vt2) | reinterpret_cast<uintptr_t>(a.out);   // LDS-DMA / output rows: 16-byte pieces
+    // the per-frame records are scalar loads (ld_uniform): nothing the kernel stores may lie over them — an output that overlaps one of
+    // them goes to the program-order kernel, which reads them behind its stores' counter
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(a.out), o1 = o0 + (uintptr_t)ob;
+    for (const void* rec : {(const void*)a.coef, (const void*)a.frame_scale, (const void*)a.kv_map}) {
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rec);
+        if (rec && r0 < o1 && o0 < r0 + 4 * (uintptr_t)a.n_frames) return false;
+    }
     return a.d == 64 && a.l % PKT == 0 && a.l >= 2 * PKT && a.ldk % 8 == 0 && a.ldvt % 8 == 0 && a.k_fs % 8 == 0 && a.vt_fs % 8 == 0 &&
            (al & 15) == 0 && kb < lim && vb < lim && k2b < lim && v2b < lim && qb < lim && ob < lim && a.ldo % 8 == 0 && a.o_fs % 8 == 0;
+}
+
+// Does this launch run as ONE persistent workgroup per CU walking several items?  The kernel owns every frame of the call (no early exits),
+// every item is whole 8-tile trips, and there are more items than CUs.  One rule for the launch and for plan_attn's default (aid_attn.hip).
+// (measured: plain S = 4096 582 -> 560 us, S = 1024 108 -> 94, inner 808 -> 800 / 129 -> 122; the 3 : 1 item mix of an OUTER call is
+//  balanced as well by the hardware's dynamic dispatch as by the static snake order: 1048 vs 1047, 160 vs 160 — one item per workgroup)
+bool attn_pp_persistent(const AidAttnArgs& a, bool multi, int* n_cu) {
+    static PerDevice<int> cus;
+    int* ncu = cus.slot();
+    if (n_cu) *n_cu = ncu ? 0 : -1;
+    if (!ncu) return false;
+    if (*ncu == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) *ncu = 256;
+    }
+    if (n_cu) *n_cu = *ncu;
+    const int items = ((a.s + 255) / 256) * a.n_frames * a.heads;
+    const int knob = tune(TUNE_ATTN_PIPE);                      // development: 0 = one item per workgroup
+    return (multi || a.mode == AID_MODE_PLAIN) && (a.l / PKT) % 8 == 0 && items > *ncu && *ncu % 8 == 0 && knob != 0;
 }
 
 hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) {
@@ -799,19 +915,9 @@ hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) 
     const void* fn = fns[ti][a.mode];
     const hipError_t e = set_max_dynamic_lds(attr_set[ti], a.mode, fn, smem);
     if (e != hipSuccess) return e;
-    const int items = p.nqb * a.n_frames * a.heads;
-    // persistent: the kernel owns every frame of the call (no early exits), every item is whole 8-tile trips, more items than CUs
-    static PerDevice<int> cus;
-    int* ncu = cus.slot();
-    if (!ncu) return hipErrorInvalidDevice;
-    if (*ncu == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) *ncu = 256;
-    }
-    const int knob = tune(TUNE_ATTN_PIPE);                      // development: 0 = one item per workgroup
-    // (measured: plain S = 4096 582 -> 560 us, S = 1024 108 -> 94, inner 808 -> 800 / 129 -> 122; the 3 : 1 item mix of an OUTER call is
-    //  balanced as well by the hardware's dynamic dispatch as by the static snake order: 1048 vs 1047, 160 vs 160 — one item per workgroup)
-    p.persist = ((multi || a.mode == AID_MODE_PLAIN) && (a.l / PKT) % 8 == 0 && items > *ncu && *ncu % 8 == 0 && knob != 0) ? 1 : 0;
+    int ncu = 0;
+    p.persist = attn_pp_persistent(a, multi, &ncu) ? 1 : 0;
+    if (ncu <= 0) return hipErrorInvalidDevice;
     // which frames walk several key segments (host's view: the AID frames of a call sit in front of its PLAIN riders, a fused call's
     // end-point frames walk their own keys only): a hint for the static balance of the persistent walk
     const int n_aid = a.n_frames - a.n_plain;
@@ -819,7 +925,7 @@ hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) 
     p.hv_units = 1;
     if (a.mode == AID_MODE_OUTER && n_aid > 2) { p.hv_lo = 1; p.hv_hi = n_aid - 1; p.hv_units = a.fused ? 3 : 2; }
     if (a.mode == AID_MODE_INNER && a.fused && n_aid > 2) { p.hv_lo = 1; p.hv_hi = n_aid - 1; p.hv_units = 2; }
-    const int grid = p.persist ? *ncu : items;
+    const int grid = p.persist ? ncu : p.nqb * a.n_frames * a.heads;
     void* kargs[] = {const_cast<AttnPPParams*>(&p)};
     return hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, smem, stream);
 }

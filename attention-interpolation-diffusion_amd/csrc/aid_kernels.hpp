@@ -122,11 +122,12 @@ enum Tune {
     TUNE_GEMM_TRI,              // 0 = never use the twelve-wave 288 x 256 engine, 1 = force it where the shape allows
     TUNE_ATTN_NW,               // 4 / 8 waves per workgroup
     TUNE_ATTN_QB,               // 1 / 2 query blocks per wave (d = 40 PLAIN)
-    TUNE_ATTN_PIPE,             // 0 / 1 software-pipelined loop
+    TUNE_ATTN_PIPE,             // 0 / 1 software-pipelined loop; ping-pong kernel: 0 = one item per workgroup (no persistent walk) — and with
+                                // that the default rule keeps PLAIN calls below 2048 keys off the ping-pong kernel (attn_pp_persistent)
     TUNE_ATTN_RES,              // 0 / 1 resident key segments
     TUNE_ATTN_RES_CHUNKS,       // > 0: chunks per (frame, head) of the resident variant
     TUNE_ATTN_ORDER,            // 0 = plain XCD order for mixed launches
-    TUNE_ATTN_V2,               // ping-pong d = 64 kernel: 0 never / 1 wherever supported; default: fused OUTER l >= 1024, everything else l >= 2048
+    TUNE_ATTN_V2,               // ping-pong d = 64 kernel: 0 never / 1 wherever supported; default: fused OUTER / INNER l >= 1024, PLAIN l >= 1024 on persistent workgroups, everything else l >= 2048
     TUNE_CU_SHARE,              // n > 1: the caller runs n independent launch streams side by side (two passes on two streams): the GEMM
                                 // engine choice plans with 1 / n of the CUs; a hint, results never depend on it
     TUNE_GEMM_RS,               // row-stationary engine for the short-K levels (aid_gemm_rs.hip): 0 = never, 1 = wherever the shape allows;
@@ -177,6 +178,8 @@ hipError_t launch_attn_plan(const AidAttnArgs& a, const AttnStep& st, hipStream_
 // d = 64 ping-pong kernel for the single-segment frames of a call (aid_attn_pp.hip); frames with more segments exit at once
 bool       attn_pp_supported(const AidAttnArgs& a);
 hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi);
+// that launch as one persistent workgroup per CU (more items than CUs, whole 8-tile trips); *n_cu: the device's CUs (<= 0: no device slot)
+bool       attn_pp_persistent(const AidAttnArgs& a, bool multi, int* n_cu);
 // d = 64 kernel for TEXT keys (<= 96 keys per segment resident in LDS; aid_attn_tx.hip): whole PLAIN / INNER / OUTER calls
 bool       attn_tx_supported(const AidAttnArgs& a);
 hipError_t attn_tx_launch(const AidAttnArgs& a, hipStream_t stream);
