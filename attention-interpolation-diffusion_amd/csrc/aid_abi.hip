@@ -75,17 +75,18 @@ struct ProfScope {          // records an event pair around one launch when prof
 
 // ---- tuning knobs (aid_kernels.hpp: enum Tune) -----------------------------------------------------
 const char* const g_tune_names[aid::TUNE_COUNT] = {"GEMM_VARIANT", "GEMM_PP", "GEMM_TRI", "ATTN_NW", "ATTN_QB", "ATTN_PIPE",
-                                                   "ATTN_RES", "ATTN_RES_CHUNKS", "ATTN_ORDER", "ATTN_V2", "CU_SHARE", "GEMM_RS", "ATTN_TX", "ATTN_TX_TILES", "GEMM_LS"};
+                                                   "ATTN_RES", "ATTN_RES_CHUNKS", "ATTN_ORDER", "ATTN_V2", "CU_SHARE", "GEMM_RS", "ATTN_TX", "ATTN_TX_TILES", "GEMM_LS",
+                                                   "GEMM_LR_PP"};
 // Largest value a knob accepts.  Every accepted value selects between kernels / launch shapes that compute THE SAME RESULT (the parity
 // suite runs under each of them); values beyond the range are refused by aid_set_tuning and ignored in the environment.  Development
 // builds (tools/dev/Makefile) widen two ranges: the attention timing ablations (kernels that skip work, "results are garbage";
 // -DAID_ABLATIONS) are ATTN_RES_CHUNKS > 100, the row-stationary GEMM's stamps / ablations (-DAID_RS_VARIANTS) GEMM_PP up to 7.
 #if defined(AID_ABLATIONS)
-const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 1000, 1, 1, 8, 1, 1, 64, 1};
+const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 1000, 1, 1, 8, 1, 1, 64, 1, 2};
 #elif defined(AID_RS_VARIANTS)
-const int g_tune_max[aid::TUNE_COUNT] = {31, 7, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1};
+const int g_tune_max[aid::TUNE_COUNT] = {31, 7, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1, 2};
 #else
-const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1};
+const int g_tune_max[aid::TUNE_COUNT] = {31, 3, 1, 8, 2, 1, 1, 64, 1, 1, 8, 1, 1, 64, 1, 2};
 #endif
 struct TuneTable {
     std::atomic<int> v[aid::TUNE_COUNT];        // independent integers: a knob flipped by one thread is seen by the launches of all

@@ -21,9 +21,9 @@
 //    launch_gemm() picks the engine per launch with a small cost model (long K loops + many tiles -> ping-pong).
 //  * aid_gemm_nt_kernel — edge path for ragged k (tests, odd context widths): 128x128 tile,
 //    register-staged, fully guarded loads, padded LDS rows.
-// The lock-step and the edge kernel carry a problem's low-rank segment (GemmLR, a second K segment before the epilogue): one kernel
-// each, the segment compiled in by the TYPE of the trailing kernel argument (GemmLR / NoLR).  Profile labels name the GemmLR
-// instantiation `<kernel>_lr`.
+// The lock-step, the edge and the 256-row ping-pong kernel carry a problem's low-rank segment (GemmLR, a second K segment before the
+// epilogue): one kernel each, the segment compiled in by the TYPE of the trailing kernel argument (GemmLR / NoLR).  Profile labels name
+// the GemmLR instantiation `<kernel>_lr`.  The 288-row kernel has none: with the segment it did not fit 256 registers.
 #include "aid_common.hpp"
 #include "aid_kernels.hpp"
 
@@ -796,6 +796,61 @@ struct PingPong : Engine<T, 256, 256, 64, 2, 2, 4> {
         rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(B + (int64_t)n0 * P.ldb), 0, 0x7fffffff, 0x00020000);
     }
 
+    // the same for the low-rank segment (GemmLR): A = LA [m, lr k] (row stride lda), B = LB [n, lr k] (row stride ldb).  What it
+    // overwrites (ra / rb, avo / bvo) is dead once the main K loop has returned.
+    __device__ __forceinline__ void set_tile_lr(int m, int n, int lda, int ldb, const T* A, const T* B, int m0, int n0) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));        // recompute the lane's rows / chunks here: shared with set_tile they would stay live across the main K loop
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int lrow = 8 * (2 * wave + j) + (ln >> 3);
+                const int c = (ln & 7) ^ swz(lrow);
+                const int row_a = (lrow >> 6) * 128 + h * 64 + (lrow & 63);
+                const int row_b = (lrow >> 5) * 64 + h * 32 + (lrow & 31);
+                avo[h * 2 + j] = min(row_a, m - 1 - m0) * (lda * 2) + c * 16;
+                bvo[h * 2 + j] = min(row_b, n - 1 - n0) * (ldb * 2) + c * 16;
+            }
+        ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A + (int64_t)m0 * lda), 0, 0x7fffffff, 0x00020000);
+        rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(B + (int64_t)n0 * ldb), 0, 0x7fffffff, 0x00020000);
+    }
+
+    // DoRA gain (GemmLRDesc.row_scale) on the eight blocks, before every epilogue step: times gain[row m] (side 1) or gain[column n]
+    // (side 2).  No control flow: both candidates are fetched (indices clamped to the gain's own length, lim), the one that does not
+    // apply is replaced by 1, and every accumulator takes both factors — x * 1 is exact, so this is the single multiply of
+    // lr_row_scale.  (With the two sides as two branches over all 128 accumulators hipcc spilled 32 of them at the join.)
+    // Scalar multiplies on purpose (Engine::store_tile).
+    static __device__ __forceinline__ float mulg(float a, float g) {
+        float t = a * g;
+        asm volatile("" : "+v"(t));
+        return t;
+    }
+    __device__ __forceinline__ void scale_rows(const float* __restrict__ gain, int side, int m0, int n0, int M, int N) {
+        mfma_fence(acc);
+        const bool bym = side == 1;
+        const int lim = bym ? M : N;
+        float gm[4], gn[2][16];
+#pragma unroll
+        for (int im = 0; im < 4; ++im) {
+            const float g = gain[min(m0 + wm + 32 * im + l31, lim - 1)];
+            gm[im] = bym ? g : 1.f;
+        }
+#pragma unroll
+        for (int in = 0; in < 2; ++in)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float g = gain[min(n0 + wn + 32 * in + hi * 4 + 8 * (r >> 2) + (r & 3), lim - 1)];
+                gn[in][r] = bym ? 1.f : g;
+            }
+#pragma unroll
+        for (int in = 0; in < 2; ++in)
+#pragma unroll
+            for (int im = 0; im < 4; ++im)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[in][im][r] = mulg(mulg(acc[in][im][r], gm[im]), gn[in][r]);
+    }
+
     // DMA j (0 / 1) of half-tile Q: 0 = B0, 1 = B1, 2 = A0, 3 = A1
     template <int Q>
     __device__ __forceinline__ void dma_one(int parity, int k0, int j) {
@@ -1417,8 +1472,12 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_ppx_kernel(const GemmGroup g,
     e.run_tile(P, C, tc.batch, tc.m0, tc.n0);
 }
 
-template <typename T, int PPV>
-__global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, const int n_big, const GemmSide sd) {
+// LRT = GemmLR: the low-rank segment of a main problem is a second set_tile_lr + K loop (the same flavour) into the same accumulators
+// — every K loop ends with no VMEM operation outstanding and the ring released — then the DoRA gain, then the shared store_tile; the
+// 128 x 128 tiles of the ragged last round take it like aid_gemm_nt_pipe_kernel.  Side tiles never carry one: a group with segments
+// and unequal K loops is planned on the lock-step engine.  NoLR: none.
+template <typename T, int PPV, typename LRT>
+__global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, const int n_big, const GemmSide sd, const LRT lr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     if ((int)blockIdx.x < sd.pad_tiles) {                          // side problems first: their long K loops start at once
         const int u = blockIdx.x;
@@ -1452,6 +1511,17 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
         if (PPV == 1)      e.template mac_rd<false>(0, P.k / 64);
         else if (PPV == 2) e.template mac_rd<true>(0, P.k / 64);
         else               e.mac(0, P.k / 64);
+        if constexpr (std::is_same<LRT, GemmLR>::value) {
+            const GemmLRDesc& L = lr.p[tc.p];
+            if (L.k > 0) {
+                e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
+                              reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
+                if (PPV == 1)      e.template mac_rd<false>(0, L.k / 64);
+                else if (PPV == 2) e.template mac_rd<true>(0, L.k / 64);
+                else               e.mac(0, L.k / 64);
+            }
+            if (L.row_scale) e.scale_rows(L.row_scale, L.side, tc.m0, tc.n0, P.m, P.n);      // DoRA gain, before every epilogue step
+        }
         e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
                      P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
     } else {
@@ -1471,6 +1541,18 @@ __global__ __launch_bounds__(512) void aid_gemm_nt_pp_kernel(const GemmGroup g, 
         e.set_tile(P, A, B, tc.m0, tc.n0);
         e.zero_acc();
         e.mac(0, P.k / 64);
+        if constexpr (std::is_same<LRT, GemmLR>::value) {
+            const GemmLRDesc& L = lr.p[tc.p];
+            if (L.k > 0) {
+                e.set_tile_lr(P.m, P.n, L.lda, L.ldb, reinterpret_cast<const T*>(L.a) + (int64_t)tc.batch * L.stride_a,
+                              reinterpret_cast<const T*>(L.b) + (int64_t)tc.batch * L.stride_b, tc.m0, tc.n0);
+                e.mac(0, L.k / 64);
+            }
+            if (L.row_scale) {
+                mfma_fence(e.acc);
+                lr_row_scale(e.acc, L.row_scale, L.side, tc.m0 + e.wm + e.l31, tc.n0 + e.wn + e.hi * 4, P.m, P.n);
+            }
+        }
         e.store_tile(P, C, tc.m0, tc.n0, P.residual ? reinterpret_cast<const T*>(P.residual) + (int64_t)tc.batch * P.stride_c : nullptr,
                      P.ln_stats ? P.ln_stats + 2 * (int64_t)tc.batch * P.stride_stats : nullptr);
     }
@@ -1557,22 +1639,22 @@ static hipError_t launch_pipe(GemmGroup& g, hipStream_t stream, const LRT& lr) {
                             128, 128, stream, 512, lr);
 }
 
-template <typename T, int PPV>
-static hipError_t launch_pp_v(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd) {
+template <typename T, int PPV, typename LRT>
+static hipError_t launch_pp_v(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd, const LRT& lr) {
     static PerDevice<int> attr_set;
     if (fill_tile_start(g, 256, 256) <= 0) return hipSuccess;
-    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(aid_gemm_nt_pp_kernel<T, PPV>), PingPong<T>::SMEM);
+    const hipError_t e = set_max_dynamic_lds(attr_set, 0, reinterpret_cast<const void*>(aid_gemm_nt_pp_kernel<T, PPV, LRT>), PingPong<T>::SMEM);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((aid_gemm_nt_pp_kernel<T, PPV>), dim3(sd.pad_tiles + n_big + n_small), dim3(512), PingPong<T>::SMEM, stream,
-                       g, n_big, sd);
+    hipLaunchKernelGGL((aid_gemm_nt_pp_kernel<T, PPV, LRT>), dim3(sd.pad_tiles + n_big + n_small), dim3(512), PingPong<T>::SMEM, stream,
+                       g, n_big, sd, lr);
     return hipGetLastError();
 }
-template <typename T>
-static hipError_t launch_pp(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd) {
+template <typename T, typename LRT>
+static hipError_t launch_pp(GemmGroup& g, hipStream_t stream, int n_big, int n_small, const GemmSide& sd, const LRT& lr) {
     switch (tune(TUNE_GEMM_PP)) {                   // K loop order (TUNE_GEMM_PP); unset and 3: 1
-        case 0:  return launch_pp_v<T, 0>(g, stream, n_big, n_small, sd);
-        case 2:  return launch_pp_v<T, 2>(g, stream, n_big, n_small, sd);
-        default: return launch_pp_v<T, 1>(g, stream, n_big, n_small, sd);
+        case 0:  return launch_pp_v<T, 0>(g, stream, n_big, n_small, sd, lr);
+        case 2:  return launch_pp_v<T, 2>(g, stream, n_big, n_small, sd, lr);
+        default: return launch_pp_v<T, 1>(g, stream, n_big, n_small, sd, lr);
     }
 }
 
@@ -1679,7 +1761,14 @@ static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide&
             break;
     }
     // `_lr` names the GemmLR instantiation of the kernel (a profiler shows it as `...kernel<..., aid::GemmLR>`)
-    if (lr) pl.symbol = engine == GemmEngine::Edge ? "aid_gemm_nt_kernel_lr" : "aid_gemm_nt_pipe_kernel_lr";
+    if (lr) {
+        switch (engine) {
+            case GemmEngine::Edge:      pl.symbol = "aid_gemm_nt_kernel_lr"; break;
+            case GemmEngine::Pp256:
+            case GemmEngine::Pp256Tail: pl.symbol = "aid_gemm_nt_pp_kernel_lr"; break;
+            default:                    pl.symbol = "aid_gemm_nt_pipe_kernel_lr"; break;
+        }
+    }
     // transposed C: the row-stationary engine and the 288-row tiles write it; side tiles run on the 128 x 128 engine, which does not
     pl.writes_trans = engine == GemmEngine::Rowstat || engine == GemmEngine::Pp288;
     for (int i = 0; i < sd.n; ++i) pl.writes_trans = pl.writes_trans && !sd.p[i].trans_rows;
@@ -1696,9 +1785,12 @@ static GemmPlan make_plan(GemmEngine engine, const GemmGroup& g, const GemmSide&
 // (the text-context projections of cross-attention: their tiles are mostly padding at 256 x 256).
 // Two CU counts: `device_cu` is the device's, `ncu` (device_cu after the CU_SHARE hint) the one the tile engines plan with.  The
 // row-stationary size rule and the GEMM_LS default look at the device's.
-// A group with low-rank segments (lr) runs on the engines that carry them: the edge kernel for ragged k, the lock-step engine (either
-// ring) otherwise.  The ping-pong engines and the row-stationary one are planned around (DESIGN.md "LoRA").
-static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool lr = false) {
+// A group with low-rank segments (lr; lr_nk = 64-deep K tiles of its longest segment) runs on the engines that carry them: the edge
+// kernel for ragged k; otherwise the same cost comparison picks between the lock-step engine (either ring) and the 256-row ping-pong
+// engine (with its 128 x 128 tail tiles), the segment's K tiles counted on both sides.  GEMM_LR_PP: 0 and unset = segments never go to
+// ping-pong, 1 = wherever the shape allows, 2 = that cost comparison decides.  GEMM_VARIANT = 31 forces plain groups only.  Groups with unequal K loops stay on the
+// lock-step engine (side tiles carry no segment); the 288-row and the row-stationary engine are planned around (DESIGN.md "LoRA").
+static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool lr = false, int lr_nk = 0) {
     GemmSide sd;
     memset(&sd, 0, sizeof(sd));
     bool k64 = true;
@@ -1764,7 +1856,7 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool 
     bool pp = false;
     PpSplit sp = {};
     if (!g.interleave && g.n_problems > 0) {
-        const int nk = g.p[0].k / 64;
+        const int nk = g.p[0].k / 64 + lr_nk;
         const int t128 = count_tiles(g, 128, 128), t256 = count_tiles(g, 256, 256);
         sp = split_pp(t256, ncu, nk);
         const double r128 = 0.5 * (double)((2 * t128 + 2 * ncu - 1) / (2 * ncu));       // rounds of 2 CUs-fulls, in halves
@@ -1775,11 +1867,16 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool 
         const double occ = (pp_tiles > 0 && pp_tiles <= ncu) ? (double)pp_tiles / ncu : 1.0;
         const double cost_pp = 5.0 + sp.rounds * (6.0 + 1.62 * nk) * (0.65 + 0.35 * occ);
         pp = cost_pp < 0.95 * cost_ls;
-        if (force == 31) pp = true;
+        if (lr) {                                   // unset = 0 until the cost runs are recorded (DESIGN.md "LoRA"); 2 keeps the cost model's answer
+            const int knob = tune(TUNE_GEMM_LR_PP);
+            if (knob != 2) pp = knob == 1;
+        } else if (force == 31) {
+            pp = true;
+        }
     }
-    if (force == 7 || lr) pp = false;
-    if (pp && prefer_ppx(g, ncu, sp.rounds)) return make_plan(GemmEngine::Pp288, g, sd, ncu);
-    if (pp) return make_plan(sp.n_small ? GemmEngine::Pp256Tail : GemmEngine::Pp256, g, sd, ncu, sp.n_big, sp.n_small);
+    if (force == 7) pp = false;
+    if (pp && !lr && prefer_ppx(g, ncu, sp.rounds)) return make_plan(GemmEngine::Pp288, g, sd, ncu);   // the 288-row engine carries no segment
+    if (pp) return make_plan(sp.n_small ? GemmEngine::Pp256Tail : GemmEngine::Pp256, g, sd, ncu, sp.n_big, sp.n_small, lr);
     // 8 waves, 64 x 32 wave tiles.  The ring: a K tile's loads are in flight for ~0.75 us whatever the launch (HBM / L2 latency), so a
     // workgroup that is alone on its CU with ONE tile ahead is latency-bound (0.75 us per K tile against 0.24 us of MFMAs).
     // Measured (profiles/r06_gemm_lockstep_rings.txt): a K tile step costs 0.5 - 0.65 us with one tile ahead and ~0.5 with three ahead —
@@ -1799,14 +1896,16 @@ static GemmPlan plan_gemm(const GemmGroup& g, int device_cu, int cu_share, bool 
 
 template <typename T>
 static hipError_t launch_plan(GemmPlan& pl, hipStream_t stream, const GemmLR* lr) {
-    const bool carries_lr = pl.engine == GemmEngine::Edge || pl.engine == GemmEngine::Lockstep || pl.engine == GemmEngine::Lockstep4;
-    if (pl.lr && !carries_lr) return hipErrorInvalidValue;             // plan_gemm never plans another engine for a segment
+    // the row-stationary and the 288-row engine carry no segment, nor do the side tiles of a ping-pong launch
+    const bool carries_lr = pl.engine != GemmEngine::Rowstat && pl.engine != GemmEngine::Pp288 && pl.sd.n == 0;
+    if (pl.lr && !carries_lr) return hipErrorInvalidValue;             // plan_gemm never plans those for a segment
     switch (pl.engine) {
         case GemmEngine::Edge:      return pl.lr ? launch_edge<T>(pl.g, stream, *lr) : launch_edge<T>(pl.g, stream, NoLR{});
         case GemmEngine::Lockstep:  return pl.lr ? launch_pipe<T, 2>(pl.g, stream, *lr) : launch_pipe<T, 2>(pl.g, stream, NoLR{});
         case GemmEngine::Lockstep4: return pl.lr ? launch_pipe<T, 4>(pl.g, stream, *lr) : launch_pipe<T, 4>(pl.g, stream, NoLR{});
         case GemmEngine::Pp256:
-        case GemmEngine::Pp256Tail: return launch_pp<T>(pl.g, stream, pl.n_big, pl.n_small, pl.sd);
+        case GemmEngine::Pp256Tail: return pl.lr ? launch_pp<T>(pl.g, stream, pl.n_big, pl.n_small, pl.sd, *lr)
+                                                 : launch_pp<T>(pl.g, stream, pl.n_big, pl.n_small, pl.sd, NoLR{});
         case GemmEngine::Pp288:     return launch_ppx<T>(pl.g, stream, pl.sd);
         case GemmEngine::Rowstat:   return gemm_rs_launch(pl.g, std::is_same<T, f16>::value ? AID_DTYPE_F16 : AID_DTYPE_BF16, pl.ncu, stream);
     }
@@ -1871,10 +1970,12 @@ hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const 
         }
     const int device_cu = num_cu();
     if (device_cu <= 0) return hipErrorInvalidDevice;
-    GemmPlan pl = plan_gemm(g, device_cu, cu_share, lr != nullptr);
+    int lr_nk = 0;
+    for (int i = 0; lr && i < g.n_problems; ++i) lr_nk = lr->p[i].k / 64 > lr_nk ? lr->p[i].k / 64 : lr_nk;
+    GemmPlan pl = plan_gemm(g, device_cu, cu_share, lr != nullptr, lr_nk);
     if (has_trans(g) && !pl.writes_trans) {
         untranspose(g, lr);
-        pl = plan_gemm(g, device_cu, cu_share, lr != nullptr);
+        pl = plan_gemm(g, device_cu, cu_share, lr != nullptr, lr_nk);
     }
     if (variant) *variant = pl.variant;
     if (symbol) *symbol = pl.symbol;

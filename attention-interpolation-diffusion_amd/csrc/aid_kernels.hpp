@@ -35,7 +35,7 @@ struct GemmGroup {                        // passed by value as the kernel argum
 };
 
 // Low-rank second K segment of a problem (AidGemmProblem.lr_*): acc += LA[m0.., 0:k] LB[n0.., 0:k]^T after the main K loop, before
-// the epilogue.  Entry i belongs to GemmGroup.p[i] (k = 0: none).  The edge, lock-step and fp32 GEMM kernels take it as a trailing
+// the epilogue.  Entry i belongs to GemmGroup.p[i] (k = 0: none).  The edge, lock-step, 256-row ping-pong and fp32 GEMM kernels take it as a trailing
 // by-value kernel argument whose TYPE compiles the segment in: GemmLR = with the segment (the profile labels call that instantiation
 // `<kernel>_lr`), NoLR = without.
 struct GemmLRDesc {
@@ -136,13 +136,15 @@ enum Tune {
     TUNE_ATTN_TX_TILES,         // > 0: 32-row tiles per wave of that kernel (sets the workgroups per (frame, head))
     TUNE_GEMM_LS,               // ring of the lock-step engine: 0 = 2 stages of 64 k, 2 workgroups / CU (rounds 1 - 5); 1 = 4 stages of 64 k,
                                 // 1 workgroup / CU; default: 1 for launches of at most one workgroup per CU with >= 16 K tiles (aid_gemm.hip)
+    TUNE_GEMM_LR_PP,            // groups with low-rank segments on the 256-row ping-pong engine: 0 = never (lock-step / edge), 1 = wherever the shape
+                                // allows, 2 = the cost model with the segment's K tiles counted (plan_gemm); default: 0, until 2 is measured
     TUNE_COUNT
 };
 int tune(int id);
 
 // picks the engine and launches it; `variant` / `symbol` receive the engine's name and its kernel symbol
 // cu_share > 1: the caller runs that many launch streams side by side (AidGemmProblem.cu_share); 0 / 1: the process-wide CU_SHARE knob decides
-// lr (optional): low-rank segments of the problems; a group with any lr->p[i].k > 0 runs on an engine that carries them (edge or lock-step)
+// lr (optional): low-rank segments of the problems; a group with any lr->p[i].k > 0 runs on an engine that carries them (edge, lock-step, 256-row ping-pong)
 hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const char** variant = nullptr, const char** symbol = nullptr,
                              int cu_share = 0, GemmLR* lr = nullptr);
 

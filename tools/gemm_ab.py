@@ -61,7 +61,7 @@ def timed(fn):
 
 
 def apply(v):
-    for name in ("GEMM_VARIANT", "GEMM_PP", "GEMM_TRI", "GEMM_RS", "CU_SHARE", "GEMM_LS"):
+    for name in ("GEMM_VARIANT", "GEMM_PP", "GEMM_TRI", "GEMM_RS", "CU_SHARE", "GEMM_LS", "GEMM_LR_PP"):
         ops.set_tuning(name, v.get(name, -1))
 
 
