@@ -39,7 +39,7 @@ class AidGemmProblem(C.Structure):
         ("residual", C.c_void_p),
         ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p), ("ln_shift", C.c_void_p),
         ("ln_side", C.c_int32), ("trans_rows", C.c_int32), ("stride_stats", C.c_int64),
-        ("cu_share", C.c_int32), ("reserved0", C.c_int32),
+        ("cu_share", C.c_int32), ("f32_split", C.c_int32),
         ("lr_a", C.c_void_p), ("lr_b", C.c_void_p), ("lr_k", C.c_int32), ("lr_lda", C.c_int32), ("lr_ldb", C.c_int32),
         ("lr_scale_side", C.c_int32), ("lr_stride_a", C.c_int64), ("lr_stride_b", C.c_int64),
         ("lr_row_scale", C.c_void_p),
@@ -81,7 +81,7 @@ class AidProcessorArgs(C.Structure):
         ("ip_begin", C.c_int32), ("ip_end", C.c_int32), ("seg_executed", C.c_int32), ("reserved2", C.c_int32),
         ("ln_wq", C.c_void_p), ("ln_wk", C.c_void_p), ("ln_wv", C.c_void_p), ("ln_const", C.c_void_p),
         ("k_cached", C.c_void_p), ("vt_cached", C.c_void_p),
-        ("cu_share", C.c_int32), ("reserved1", C.c_int32),
+        ("cu_share", C.c_int32), ("f32_split", C.c_int32),
         ("attn_bias", C.c_void_p), ("attn_bias_fs", C.c_int64), ("attn_bias_hs", C.c_int32), ("attn_bias_rs", C.c_int32),
         ("lora_down_x", C.c_void_p), ("lora_down_ctx", C.c_void_p), ("lora_down_o", C.c_void_p),
         ("lora_up_q", C.c_void_p), ("lora_up_k", C.c_void_p), ("lora_up_v", C.c_void_p), ("lora_up_o", C.c_void_p),

@@ -132,6 +132,7 @@ int check_problem(const AidGemmProblem& q) {
         if (q.lr_k == 0 || (q.lr_scale_side != 1 && q.lr_scale_side != 2) || !aligned4(q.lr_row_scale)) return AID_ERR_ARG;
         if (q.trans_rows && q.lr_scale_side != 2) return AID_ERR_ARG;     // the flat value projection: the weight is b
     }
+    if (q.f32_split != 0 && q.f32_split != 1) return AID_ERR_ARG;         // float32 matmul precision
     return AID_OK;
 }
 
@@ -209,6 +210,7 @@ int check_processor(const AidProcessorArgs& a) {
     if (a.attn_bias && ((a.fused && a.mode != AID_MODE_PLAIN) || a.ip || a.attn_bias_fs < 0 || a.attn_bias_hs < 0 || a.attn_bias_rs < 0))
         return AID_ERR_ARG;                            // the mask covers one key segment (aid_hip.h); the image branch has no mask to take
     if (!(a.ln_eps >= 0.f) || a.cu_share < 0 || a.cu_share > 8) return AID_ERR_ARG;
+    if ((a.f32_split != 0 && a.f32_split != 1) || (a.f32_split && a.dtype != AID_DTYPE_F32)) return AID_ERR_ARG;
     if (a.ln_eps > 0.f) {
         if (!aid::layernorm_width_supported(a.c)) return AID_ERR_SHAPE;
         if ((a.ln_gamma && !aligned16(a.ln_gamma)) || (a.ln_beta && !aligned16(a.ln_beta))) return AID_ERR_SHAPE;
@@ -357,10 +359,15 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
     aid::GemmLR lr;
     memset(&lr, 0, sizeof(lr));
     bool has_lr = false;
+    // float32 matmul precision "high" (f32_split) is a permission: the split kernel runs a group only if every problem grants it and the
+    // group is plain (that kernel carries neither the low-rank segment nor the folded LayerNorm); every other group runs exact
+    bool split = dtype == AID_DTYPE_F32;
     for (int i = 0; i < n_problems; ++i) {
         const AidGemmProblem& q = problems[i];
         int rc = check_problem(q);
         if (rc != AID_OK) return rc;
+        if (q.f32_split && dtype != AID_DTYPE_F32) return AID_ERR_ARG;
+        if (!q.f32_split || q.ln_stats || q.lr_k > 0) split = false;
         if (q.lr_k > 0) {
             aid::GemmLRDesc& L = lr.p[i];
             L.a = q.lr_a; L.b = q.lr_b; L.k = q.lr_k; L.lda = q.lr_lda; L.ldb = q.lr_ldb;
@@ -399,7 +406,11 @@ int aid_gemm_nt(const AidGemmProblem* problems, int n_problems, int dtype, void*
     hipError_t e;
     {
         ProfScope ps(static_cast<hipStream_t>(stream), "aid_gemm_nt", flops, dtype == AID_DTYPE_F32 ? 2.0 * bytes : bytes);
-        if (dtype == AID_DTYPE_F32) {
+        if (split) {
+            e = aid::gemm_f32x3_launch(g, static_cast<hipStream_t>(stream));
+            g_gemm_variant = "f32x3";
+            ps.rename("aid_gemm_f32x3_kernel");
+        } else if (dtype == AID_DTYPE_F32) {
             e = aid::gemm_f32_launch(g, static_cast<hipStream_t>(stream), has_lr ? &lr : nullptr);
             g_gemm_variant = "f32";
             ps.rename(has_lr ? "aid_gemm_f32_kernel_lr" : "aid_gemm_f32_kernel");
@@ -610,6 +621,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
             ++nd;
         }
         pd[0].cu_share = a.cu_share;
+        for (int i = 0; i < nd; ++i) pd[i].f32_split = a.f32_split;
         rc = aid_gemm_nt(pd, nd, a.dtype, stream);
         if (rc != AID_OK) return rc;
     }
@@ -696,6 +708,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
         npr -= 2;
         pr[0].cu_share = a.cu_share;
     }
+    for (int i = 0; i < npr; ++i) pr[i].f32_split = a.f32_split;
     rc = aid_gemm_nt(pr, npr, a.dtype, stream);
     if (rc != AID_OK) return rc;
 
@@ -753,6 +766,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
     po.m = a.n_frames * a.s; po.n = a.c; po.k = a.c;
     po.lda = a.c; po.ldb = a.c; po.ldc = a.c; po.batch = 1;
     po.cu_share = a.cu_share;
+    po.f32_split = a.f32_split;
     if (a.lora_r_o) {
         AidGemmProblem pd;
         memset(&pd, 0, sizeof(pd));
@@ -760,6 +774,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
         pd.m = a.n_frames * a.s; pd.n = a.lora_r_o; pd.k = a.c;
         pd.lda = a.c; pd.ldb = a.c; pd.ldc = a.lora_r_o; pd.batch = 1;
         pd.cu_share = a.cu_share;
+        pd.f32_split = a.f32_split;
         rc = aid_gemm_nt(&pd, 1, a.dtype, stream);
         if (rc != AID_OK) return rc;
         po.lr_a = ws + cv.uo; po.lr_lda = a.lora_r_o;

@@ -154,6 +154,9 @@ hipError_t gemm_rs_launch(const GemmGroup& g, int dtype, int ncu, hipStream_t st
 
 // float32 storage path (aid_f32.hip)
 hipError_t gemm_f32_launch(GemmGroup& g, hipStream_t stream, const GemmLR* lr = nullptr);
+// the same GEMM with every operand element split into two bf16 halves, three bf16 products (aid_f32x3.hip; AidGemmProblem.f32_split);
+// plain groups only: no low-rank segment, no folded LayerNorm
+hipError_t gemm_f32x3_launch(GemmGroup& g, hipStream_t stream);
 hipError_t attn_f32_launch(const AidAttnArgs& a, hipStream_t stream);
 hipError_t lerp_kv_f32_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                               int end, int64_t k_fs, int64_t vt_fs, hipStream_t stream);

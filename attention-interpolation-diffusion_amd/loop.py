@@ -18,7 +18,7 @@ unconditional plain) are captured once into hipGraphs and replayed per step, so 
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional, Sequence
+from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -154,13 +154,13 @@ class AidDenoiseLoop:
         self.guidance_scale = guidance_scale
         self.use_graphs = use_graphs
         self.combine = combine or self._cfg
-        self._graphs: Dict[str, torch.cuda.CUDAGraph] = {}
+        self._graphs: Dict[Tuple[str, int], torch.cuda.CUDAGraph] = {}
         self.fallback_reason: Optional[str] = None        # set when a capture failed and the loop went eager
         from . import ops
         self._ws = ops.WorkspaceOwner()          # the captures' workspaces are dropped with this loop (and its graphs)
         self._warmed: set = set()
         self._cap = None
-        self._outs: Dict[str, object] = {}
+        self._outs: Dict[Tuple[str, int], object] = {}
 
     def _cfg(self, text, uncond):
         if isinstance(text, dict):
@@ -214,7 +214,9 @@ class AidDenoiseLoop:
     def _run(self, which: str):
         if not self.use_graphs:
             return self._pass(which)
-        g = self._graphs.get(which)
+        from . import ops
+        gk = (which, ops.f32_split_code())              # a graph holds the kernels of the float32 matmul precision it was captured under
+        g = self._graphs.get(gk)
         if g is None:
             cur = torch.cuda.current_stream()
             if self._cap is None:
@@ -228,7 +230,7 @@ class AidDenoiseLoop:
             g = torch.cuda.CUDAGraph()
             try:
                 with self._ws, torch.cuda.graph(g, stream=cap):
-                    self._outs[which] = self._pass(which)
+                    self._outs[gk] = self._pass(which)
             except RuntimeError as e:
                 # a pass that cannot be captured (a collective of the end-point-exchange layout on a stack whose RCCL does not record
                 # into graphs, a foreign UNet that synchronises): the loop goes on eagerly, loudly (pipelines._PassGraphs does the same)
@@ -245,9 +247,9 @@ class AidDenoiseLoop:
                 except RuntimeError as e2:
                     raise RuntimeError(f"device unusable after a failed stream capture ({self.fallback_reason})") from e2
                 return self._pass(which)
-            self._graphs[which] = g
+            self._graphs[gk] = g
         g.replay()
-        return self._outs[which]
+        return self._outs[gk]
 
     def aid_on(self, i: int) -> bool:
         return i < self.warmup_steps

@@ -97,6 +97,24 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+# ---- float32 matmul precision -----------------------------------------------------------------------------------------------
+# torch.set_float32_matmul_precision: "highest" = exact fp32 products (the default), "high" = every float32 number taken as the sum of
+# two bfloat16 numbers, three bf16 products (AidGemmProblem.f32_split, csrc/aid_f32x3.hip).  "medium" only PERMITS less precision than
+# "high"; it runs the same split.  Projections of float32 tensors only: 16-bit tensors never carry the field, the attention core's
+# products stay exact.
+F32_PRECISIONS = {"highest": 0, "high": 1, "medium": 1}
+
+
+def f32_split_code(f32_precision: Optional[str] = None) -> int:
+    """AidGemmProblem.f32_split of a float32 launch: ``None`` reads ``torch.get_float32_matmul_precision()`` now."""
+    if f32_precision is None:
+        f32_precision = torch.get_float32_matmul_precision()
+    try:
+        return F32_PRECISIONS[f32_precision]
+    except (KeyError, TypeError):
+        raise ValueError(f"f32_precision must be None, 'highest', 'high' or 'medium'; got {f32_precision!r}") from None
+
+
 # ---- scratch memory --------------------------------------------------------------------------------------------------------
 # One workspace per (device, stream): kernels on one stream run in order, so reuse is safe.  Stream captures get their OWN workspace,
 # keyed by the capture's id (aid_stream_capture_id) and never handed to eager calls or to another capture, even when torch recycles the
@@ -239,7 +257,7 @@ def current_cu_share() -> int:
 def gemm_nt(problems: Sequence[dict]) -> None:
     """Grouped C = A @ B^T (+ bias) (+ residual, added after the rounding).  Each problem: dict(a=[.., m, k],
     b=[n, k] or [batch, n, k], c=out tensor, bias=None|[n], residual=None|like c, batch=1, m, n, k, lda, ldb, ldc,
-    stride_a, stride_b, stride_c)."""
+    stride_a, stride_b, stride_c[, f32_precision=None|"highest"|"high"|"medium": float32 operands only, ``f32_split_code``])."""
     lib = _lib.load()
     n = len(problems)
     arr = (AidGemmProblem * n)()
@@ -262,6 +280,9 @@ def gemm_nt(problems: Sequence[dict]) -> None:
         q.stride_a, q.stride_b, q.stride_c = p.get("stride_a", 0), p.get("stride_b", 0), p.get("stride_c", 0)
         q.trans_rows = int(p.get("trans_rows", 0))      # C transposed per frame of that many rows (aid_hip.h)
         q.cu_share = current_cu_share()
+        split = f32_split_code(p.get("f32_precision"))      # (a bad value raises whatever the dtype)
+        if dt == DTYPE_F32:
+            q.f32_split = split
         if p.get("ln_stats") is not None:       # folded LayerNorm: dict(ln_stats=, ln_colsum=, ln_shift=, ln_side=1|2[, stride_stats=])
             for t_ in (p["ln_stats"], p["ln_colsum"], p["ln_shift"]):
                 _require_gpu(t_)
@@ -290,8 +311,10 @@ def gemm_nt(problems: Sequence[dict]) -> None:
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
-           out: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T + bias (+ residual) on the HIP GEMM (x [..., k] contiguous, w [n, k] contiguous)."""
+           out: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+           f32_precision: Optional[str] = None) -> torch.Tensor:
+    """y = x @ w.T + bias (+ residual) on the HIP GEMM (x [..., k] contiguous, w [n, k] contiguous).  ``f32_precision``: float32
+    tensors only, None = ``torch.get_float32_matmul_precision()`` (``f32_split_code``)."""
     assert x.is_contiguous() and w.is_contiguous()
     k = x.shape[-1]
     n = w.shape[0]
@@ -300,7 +323,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         out = torch.empty(*x.shape[:-1], n, dtype=x.dtype, device=x.device)
     if residual is not None and (residual.shape != out.shape or residual.dtype != out.dtype or not residual.is_contiguous()):
         raise ValueError("residual must be a contiguous tensor shaped like the output")
-    gemm_nt([dict(a=x, b=w, c=out, bias=bias, residual=residual, m=m, n=n, k=k, lda=k, ldb=k, ldc=n)])
+    gemm_nt([dict(a=x, b=w, c=out, bias=bias, residual=residual, m=m, n=n, k=k, lda=k, ldb=k, ldc=n, f32_precision=f32_precision)])
     return out
 
 
@@ -378,12 +401,14 @@ def dora_gain(w: torch.Tensor, a_pack: torch.Tensor, b_pack: torch.Tensor, magni
 
 def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: int = 0,
                lora_k: Optional[Tuple[torch.Tensor, ...]] = None,
-               lora_v: Optional[Tuple[torch.Tensor, ...]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               lora_v: Optional[Tuple[torch.Tensor, ...]] = None,
+               f32_precision: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """k = e @ wk.T  [F, L, C]  and  V^T = wv @ e^T  [F, C, Lp]  (Lp = L rounded up to 8) in one launch.
     ``extra_rows``: allocate that many more (uninitialised) frame rows behind the F projected ones — room for the
     end-point frames' keys / values a rank receives from their owners (dist.EndpointExchange).
     ``lora_k`` / ``lora_v`` = (A_pack, B_pack[, gain]) (lora.pack): the adapters' terms are added in the same accumulators; e is
-    projected down once, U = e [A_k; A_v]^T, in one launch before.  ``gain`` (DoRA, fp32 [C] or None) multiplies the accumulator."""
+    projected down once, U = e [A_k; A_v]^T, in one launch before.  ``gain`` (DoRA, fp32 [C] or None) multiplies the accumulator.
+    ``f32_precision``: float32 tensors only, None = ``torch.get_float32_matmul_precision()`` (``f32_split_code``)."""
     f, l, cc = e.shape
     c = wk.shape[0]
     lp = (l + 7) // 8 * 8
@@ -397,7 +422,7 @@ def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: 
     if rk + rv:
         down = torch.cat([p[0] for p in (lora_k, lora_v) if p is not None], 0) if rk and rv else (lora_k or lora_v)[0]
         u = torch.empty(f * l, rk + rv, dtype=e.dtype, device=e.device)
-        gemm_nt([dict(a=e, b=down, c=u, m=f * l, n=rk + rv, k=cc, lda=cc, ldb=cc, ldc=rk + rv)])
+        gemm_nt([dict(a=e, b=down, c=u, m=f * l, n=rk + rv, k=cc, lda=cc, ldb=cc, ldc=rk + rv, f32_precision=f32_precision)])
     if l % 8 == 0:          # flat value projection, transposed epilogue (tile count of the key projection: whole CU rounds)
         pv = dict(a=e, b=wv, c=vt, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=lp, stride_c=c * lp, trans_rows=l)
         if rv:
@@ -410,6 +435,7 @@ def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: 
     pk = dict(a=e, b=wk, c=k, m=f * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c)
     if rk:
         pk["lr"] = dict(a=u, b=lora_k[1], k=rk, lda=rk + rv, ldb=rk, row_scale=gk, scale_side=2)
+    pk["f32_precision"] = pv["f32_precision"] = f32_precision
     gemm_nt([pk, pv])
     return k, vt
 
@@ -531,7 +557,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   residual: Optional[torch.Tensor] = None, seg_executed: int = 0,
                   ip: Optional[dict] = None, ln_folded: Optional[tuple] = None,
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                  attn_bias: Optional[torch.Tensor] = None, lora=None) -> torch.Tensor:
+                  attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -549,8 +575,11 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``lora``: unmerged LoRA adapters of the four projections (``lora.LoraArgs``, AidProcessorArgs.lora_*): each projection with a
     rank computes  in W^T + round(in A_pack^T) B_pack^T  in its GEMM accumulator; refused with ``ln_folded`` and, on k / v, with
     ``kv_cached`` (the cached keys must already hold the adapter term).  ``lora.gains`` (DoRA, AidProcessorArgs.lora_gain_*): the
-    fp32 row gain of each projection's adapter, or None."""
+    fp32 row gain of each projection's adapter, or None.
+    ``f32_precision``: float32 tensors only — the precision of every projection GEMM of the call (AidProcessorArgs.f32_split), None =
+    ``torch.get_float32_matmul_precision()`` at call time; the attention core stays exact."""
     lib = _lib.load()
+    split = f32_split_code(f32_precision)
     ipt = ip or {}
     dev = _require_gpu(x, ctx, wq, wk, wv, wo, bo, coef, ctx_map, out, residual, attn_bias, *(ln[:2] if ln else ()),
                        ipt.get("tokens"), ipt.get("wk"), ipt.get("wv"), ipt.get("map"), ipt.get("frame_scale"))
@@ -653,6 +682,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                     raise ValueError("DoRA gains are contiguous float32 [C] tensors of projections that have a rank")
         a.lora_gain_q, a.lora_gain_k, a.lora_gain_v, a.lora_gain_o = (_ptr(t_) for t_ in gains)
     a.cu_share = current_cu_share()
+    if dt == DTYPE_F32:
+        a.f32_split = split
     nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):
         if nbytes == 0:

@@ -199,9 +199,16 @@ class _PassGraphs:
             out = fn(**static)
         return graph, static, out
 
+    @staticmethod
+    def _key(key):
+        """A captured pass holds the kernels of the float32 matmul precision it was captured under (the processors read
+        ``torch.get_float32_matmul_precision()`` per call): a change of the global re-captures instead of replaying stale graphs."""
+        return (key, ops.f32_split_code())
+
     def run(self, key, fn: Callable, **inputs: torch.Tensor):
         if not self.enabled:
             return fn(**inputs)
+        key = self._key(key)
         ent = self._ent.get(key)
         if ent is None:
             try:

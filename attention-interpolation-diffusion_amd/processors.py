@@ -361,8 +361,10 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
     if None in ks:
         return None
     lk, lv = lora.kv_packs(attn, ctx.dtype, ctx.device)          # unmerged LoRA of to_k / to_v: part of the projection and of the key
+    # (float32: entries projected under one torch.set_float32_matmul_precision setting must not serve the other)
     key = ks + (tuple(ehs.shape), ehs.dtype, tuple(idx) if idx is not None else None,
-                None if lk is None else lk.key, None if lv is None else lv.key)
+                None if lk is None else lk.key, None if lv is None else lv.key,
+                ops.f32_split_code() if ctx.dtype == torch.float32 else 0)
     try:
         per = _KV_CACHE.get(attn)
         if per is None:
@@ -376,7 +378,7 @@ def _text_kv(attn, ehs, ctx: torch.Tensor, idx, wk: torch.Tensor, wv: torch.Tens
         kw = {} if lk is None and lv is None else dict(lora_k=None if lk is None else (lk.a, lk.b, lk.gain),
                                                        lora_v=None if lv is None else (lv.a, lv.b, lv.gain))
         k, vt = ops.project_kv(ctx, wk, wv, **kw)
-        for old in [kk for kk in per if kk[0][0] == key[0][0] and kk[3:6] == key[3:6]]:
+        for old in [kk for kk in per if kk[0][0] == key[0][0] and kk[3:6] == key[3:6] and kk[8] == key[8]]:
             per.pop(old, None)            # the same tensor at an older version (or with replaced weights)
 
         def _drop(_ref, per=per, key=key):

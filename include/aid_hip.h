@@ -113,7 +113,16 @@ typedef struct AidGemmProblem {
     /* conditional and the unconditional UNet call of a step on two streams), so this launch should plan with 1 / n of the CUs —    */
     /* a per-call hint (two host threads may pass different values); results never depend on it.  0 / 1: the whole device.          */
     int32_t      cu_share;
-    int32_t      reserved0;
+    /* float32 matmul precision (AID_DTYPE_F32 only; torch.set_float32_matmul_precision).  This is the field that was `reserved0`, which */
+    /* callers left zero: layout and ABI version are unchanged.  0 (a zeroed struct): exact fp32 products on v_mfma_f32_32x32x2_f32.      */
+    /* 1 ("high"): every operand element is taken as the sum of two bfloat16 numbers,                                                     */
+    /*     Xh = bf16_rne(X),  Xl = bf16_rne(X - float(Xh))        (round-to-nearest-even both; the subtraction is exact in fp32)       */
+    /*     C = epilogue( sum_k (Ah Bh + Al Bh + Ah Bl) )          (three v_mfma_f32_32x32x16_bf16 products, exact, fp32 accumulation)  */
+    /* with the epilogue of the exact kernel: ~4e-6 rel-L2 of the fp64 product instead of ~3e-7, at 1.2 - 2.4 x the exact kernel's rate. */
+    /* "May use": a launch runs split only if EVERY problem of the group asks for it and none carries ln_stats or a low-rank segment;  */
+    /* every other group runs exact (never an error, nothing dropped).  An infinite or over-range element (|x| > 3.39e38) gives NaN    */
+    /* where the exact kernel gives inf.  AID_ERR_ARG: a value outside {0, 1}; a non-zero value with a 16-bit dtype.                   */
+    int32_t      f32_split;
     /* ABI v9 — low-rank second K segment (lr_k == 0: none): an unmerged LoRA adapter of the projection,                     */
     /*     C = epilogue( scale * (A B^T + LA LB^T) + bias ... )                                                               */
     /* LA = lr_a [m, lr_k] (row stride lr_lda), LB = lr_b [n, lr_k] (row stride lr_ldb), batch b at lr_a + b * lr_stride_a /   */
@@ -329,7 +338,10 @@ typedef struct AidProcessorArgs {
     const void*  k_cached;
     const void*  vt_cached;
     int32_t      cu_share;       /* ABI v7: see AidGemmProblem.cu_share — handed to every GEMM launch of the call            */
-    int32_t      reserved1;
+    /* float32 matmul precision of every projection GEMM the call launches (q / k / v / out, the image-token k / v, the LoRA down     */
+    /* projections): AidGemmProblem.f32_split, same values, same errors (the field that was reserved1: zero = exact, as before).      */
+    /* The attention core's two products stay exact.                                                                                   */
+    int32_t      f32_split;
     /* ABI v8: additive score bias of the text attention (attention_mask), see AidAttnArgs.bias; not with `fused`, not with `ip` */
     const void*  attn_bias;
     int64_t      attn_bias_fs;
@@ -395,7 +407,7 @@ int         aid_abi_version(void);
 const char* aid_strerror(int code);
 /* name of the kernel variant the last aid_attn_fwd call on this thread launched (for profiling) */
 const char* aid_last_attn_variant(void);
-/* same for the last aid_gemm_nt launch: "lockstep128", "pingpong256" (+ "+tail128") or "edge" */
+/* same for the last aid_gemm_nt launch: "lockstep128", "pingpong256" (+ "+tail128") or "edge"; float32: "f32" (exact) or "f32x3" (split) */
 const char* aid_last_gemm_variant(void);
 /* Thread safety (ABI v7): every entry point may be called from several host threads at once, each on its own stream with its own
  * workspace.  The tuning table is a set of independent atomic integers (a knob flipped by one thread is seen by the launches of all),
