@@ -879,18 +879,12 @@ bool attn_pp_supported(const AidAttnArgs& a) {
 // (measured: plain S = 4096 582 -> 560 us, S = 1024 108 -> 94, inner 808 -> 800 / 129 -> 122; the 3 : 1 item mix of an OUTER call is
 //  balanced as well by the hardware's dynamic dispatch as by the static snake order: 1048 vs 1047, 160 vs 160 — one item per workgroup)
 bool attn_pp_persistent(const AidAttnArgs& a, bool multi, int* n_cu) {
-    static PerDevice<int> cus;
-    int* ncu = cus.slot();
-    if (n_cu) *n_cu = ncu ? 0 : -1;
-    if (!ncu) return false;
-    if (*ncu == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) *ncu = 256;
-    }
-    if (n_cu) *n_cu = *ncu;
+    int ncu = device_cu_count();
+    if (ncu <= 0) ncu = 256;
+    if (n_cu) *n_cu = ncu;
     const int items = ((a.s + 255) / 256) * a.n_frames * a.heads;
     const int knob = tune(TUNE_ATTN_PIPE);                      // development: 0 = one item per workgroup
-    return (multi || a.mode == AID_MODE_PLAIN) && (a.l / PKT) % 8 == 0 && items > *ncu && *ncu % 8 == 0 && knob != 0;
+    return (multi || a.mode == AID_MODE_PLAIN) && (a.l / PKT) % 8 == 0 && items > ncu && ncu % 8 == 0 && knob != 0;
 }
 
 hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) {
@@ -917,7 +911,6 @@ hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi) 
     if (e != hipSuccess) return e;
     int ncu = 0;
     p.persist = attn_pp_persistent(a, multi, &ncu) ? 1 : 0;
-    if (ncu <= 0) return hipErrorInvalidDevice;
     // which frames walk several key segments (host's view: the AID frames of a call sit in front of its PLAIN riders, a fused call's
     // end-point frames walk their own keys only): a hint for the static balance of the persistent walk
     const int n_aid = a.n_frames - a.n_plain;

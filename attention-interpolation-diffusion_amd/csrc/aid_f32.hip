@@ -7,21 +7,20 @@
 // HIP path against the reference's OWN float32 outputs (tests/golden/*.npz) at rounding-noise level, not through a storage-type
 // tolerance.  Probabilities are NOT rounded before the PV product (the reference's float32 `get_attention_scores` does not either).
 //
-//   aid_gemm_f32_kernel     C = scale * A B^T (+ bias) (+ residual), 64 x 64 x 16 tiles, four waves of one 32 x 32 block; every
-//                           AidGemmProblem option (batches, transposed-per-frame output, folded LayerNorm constants); its GemmLR
-//                           instantiation (profile label aid_gemm_f32_kernel_lr) runs the low-rank segment as a second K loop
+//   aid_gemm_f32_kernel     C = scale * A B^T (+ bias) (+ residual), 128 x 128 x 16 or 64 x 64 x 16 tiles, four waves of 2 x 2 or one
+//                           32 x 32 block; every AidGemmProblem option (batches, transposed-per-frame output, folded LayerNorm
+//                           constants); its GemmLR instantiation (profile label aid_gemm_f32_kernel_lr) runs the low-rank segment
+//                           through the same K loop.  The tile walk, the epilogue and the host's tile rule are aid_gemm_f32.hpp's,
+//                           shared with the split kernel (aid_f32x3.hip); here: the fp32 staging and the exact MFMA block
 //                           [attn.to_q / to_k / to_v / to_out[0], interpolation.py:613, 623-624, 666]
 //   aid_attn_f32_kernel<D>  flash-style interpolated attention, 128 query rows per workgroup (32 per wave), 32-key tiles through LDS,
 //                           swapped products (a lane owns one query row), online softmax in fp32; PLAIN / INNER / OUTER, fused or
 //                           pure, riders, maps, accumulate — OUTER as two independent softmax passes like the reference writes it
 //                           [interpolation.py:626-664, 760-790]
 //   aid_lerp_kv_f32_kernel  K / V^T of the interior frames for INNER [interpolation.py:772-775]
-#include "aid_common.hpp"
-#include "aid_kernels.hpp"
+#include "aid_gemm_f32.hpp"
 
 #include <string.h>
-
-#include <type_traits>
 
 namespace aid {
 
@@ -46,209 +45,98 @@ __device__ __forceinline__ f32x16 mfma32f(float a, float b, const f32x16& c) {
 // instruction takes 64 cycles, so the smaller tile's doubled LDS traffic per MFMA costs nothing and four times the workgroups are in flight.
 constexpr int FBK = 16, FLD = FBK + 4;
 
-// LRT = GemmLR: the problem's low-rank segment runs through a second K loop before the epilogue; NoLR: no segment.  One kernel with the
-// body in the __global__ function, like the edge GEMM's (aid_gemm.hip: aid_gemm_nt_kernel).
+// LRT = GemmLR: the problem's low-rank segment runs through the K loop a second time before the epilogue; NoLR: no segment.
 template <int FBM, typename LRT>
 __global__ __launch_bounds__(256) void aid_gemm_f32_kernel(const GemmGroup g, const LRT lr) {
-    constexpr int FBN = FBM, WT = FBM / 2, NB = WT / 32, RS = FBM / 64;       // wave tile, 32-blocks per side, staging rows per thread
-    __shared__ __attribute__((aligned(16))) float smem[2 * (FBM + FBN) * FLD];
-    // ---- block -> (problem, batch, tile)
-    int p = 0;
-#pragma unroll
-    for (int i = 1; i < AID_GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.n_problems && (int)blockIdx.x >= g.tile_start[i]) p = i;
-    const GemmDesc& P = g.p[p];
-    int rem = blockIdx.x - g.tile_start[p];
-    const int tiles_n = (P.n + FBN - 1) / FBN, tiles_m = (P.m + FBM - 1) / FBM;
-    const int batch = rem / (tiles_m * tiles_n);
-    rem -= batch * tiles_m * tiles_n;
-    // column tiles of one row panel are neighbours in the grid: they share the A panel in L2
-    const int m0 = (rem / tiles_n) * FBM, n0 = (rem % tiles_n) * FBN;
-    const float* __restrict__ A = reinterpret_cast<const float*>(P.a) + (int64_t)batch * P.stride_a;
-    const float* __restrict__ B = reinterpret_cast<const float*>(P.b) + (int64_t)batch * P.stride_b;
-    float* __restrict__ C = reinterpret_cast<float*>(P.c) + (int64_t)batch * P.stride_c;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, hi = lane >> 5;
-    const int wm = (wave >> 1) * WT, wn = (wave & 1) * WT;
-    // staging: thread -> (row = tid / 4 [+ 64], k quad = tid % 4); rows past the matrix are clamped (their products are never stored)
-    const int srow = tid >> 2, sq = (tid & 3) * 4;
+    typedef F32Tile<FBM> Tile;
+    constexpr int NB = Tile::NB, RS = Tile::RS;
+    __shared__ __attribute__((aligned(16))) float smem[2 * (FBM + FBM) * FLD];
+    const Tile t(g);
+    const GemmDesc& P = t.P;
+    const int sq = (threadIdx.x & 3) * 4;                  // staging: a thread's k quad
     const float* ap[RS];
     const float* bp[RS];
-#pragma unroll
-    for (int i = 0; i < RS; ++i) {
-        ap[i] = A + (int64_t)min(m0 + srow + 64 * i, P.m - 1) * P.lda + sq;
-        bp[i] = B + (int64_t)min(n0 + srow + 64 * i, P.n - 1) * P.ldb + sq;
-    }
-
-    f32x16 acc[NB][NB];                                    // [n block][m block]
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    t.rows(P.a, P.stride_a, P.lda, P.b, P.stride_b, P.ldb, sq, ap, bp);
+    typename Tile::Acc acc;
+    Tile::zero(acc);
 
     f32x4 ra[RS], rb[RS];
+    // the loads of the K tiles, in order: the row pointers walk along (an offset added to fixed pointers compiles to address arithmetic
+    // between the barrier and the loads, 3 - 5 % on the launches of one workgroup per CU, whose K steps wait for exactly these loads)
     auto load = [&](int k0) {                              // k is a multiple of 8 (aid_hip.h): a quad is inside the row or past it
         const bool in = k0 + sq < P.k;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < RS; ++i) {
-            ra[i] = in ? *reinterpret_cast<const f32x4*>(ap[i] + k0) : z;
-            rb[i] = in ? *reinterpret_cast<const f32x4*>(bp[i] + k0) : z;
+            ra[i] = in ? *reinterpret_cast<const f32x4*>(ap[i]) : z;
+            rb[i] = in ? *reinterpret_cast<const f32x4*>(bp[i]) : z;
+            ap[i] += FBK;
+            bp[i] += FBK;
         }
     };
     auto store = [&](int buf) {
-        float* As = smem + buf * (FBM + FBN) * FLD;
+        float* As = smem + buf * (FBM + FBM) * FLD;
         float* Bs = As + FBM * FLD;
 #pragma unroll
         for (int i = 0; i < RS; ++i) {
-            *reinterpret_cast<f32x4*>(As + (srow + 64 * i) * FLD + sq) = ra[i];
-            *reinterpret_cast<f32x4*>(Bs + (srow + 64 * i) * FLD + sq) = rb[i];
+            *reinterpret_cast<f32x4*>(As + (t.srow + 64 * i) * FLD + sq) = ra[i];
+            *reinterpret_cast<f32x4*>(Bs + (t.srow + 64 * i) * FLD + sq) = rb[i];
         }
     };
-
-    const int nk = (P.k + FBK - 1) / FBK;
-    load(0);
-    store(0);
-    __syncthreads();
-    // The MFMA block of a K tile is written out in both K loops: factored into a lambda or a device function (tried both), the NoLR
-    // instantiation of the 128 x 128 tile compiles to other code than before.
-    for (int t = 0; t < nk; ++t) {
-        if (t + 1 < nk) load((t + 1) * FBK);
-        const float* As = smem + (t & 1) * (FBM + FBN) * FLD;
-        const float* Bs = As + FBM * FLD;
-#pragma unroll
-        for (int kg = 0; kg < 2; ++kg) {                   // two groups of 8 k per tile
-            f32x4 fa[NB], fb[NB];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                fa[i] = *reinterpret_cast<const f32x4*>(As + (wm + 32 * i + l31) * FLD + 8 * kg + 4 * hi);
-                fb[i] = *reinterpret_cast<const f32x4*>(Bs + (wn + 32 * i + l31) * FLD + 8 * kg + 4 * hi);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < NB; ++i)
-#pragma unroll
-                    for (int j = 0; j < NB; ++j)           // D[n][m]: lane (m = l31, hi) ends up with n = 8 g + 4 hi + e
-                        acc[i][j] = mfma32f(fb[i][e], fa[j][e], acc[i][j]);
-        }
-        if (t + 1 < nk) store((t + 1) & 1);
+    // acc += (nk tiles of 16 k, staged by `ld`): the next tile's loads are in flight during the current tile's MFMAs
+    auto k_loop = [&](int nk, auto&& ld) {
+        ld(0);
+        store(0);
         __syncthreads();
-    }
-    if constexpr (std::is_same<LRT, GemmLR>::value) {      // acc += LA LB^T: the same loop on the low-rank operands (k % 64 == 0)
-        const GemmLRDesc& L = lr.p[p];
-        const float* LA = reinterpret_cast<const float*>(L.a) + (int64_t)batch * L.stride_a;
-        const float* LB = reinterpret_cast<const float*>(L.b) + (int64_t)batch * L.stride_b;
-#pragma unroll
-        for (int i = 0; i < RS; ++i) {
-            ap[i] = LA + (int64_t)min(m0 + srow + 64 * i, P.m - 1) * L.lda + sq;
-            bp[i] = LB + (int64_t)min(n0 + srow + 64 * i, P.n - 1) * L.ldb + sq;
-        }
-        auto lr_load = [&](int k0) {
-#pragma unroll
-            for (int i = 0; i < RS; ++i) {
-                ra[i] = *reinterpret_cast<const f32x4*>(ap[i] + k0);
-                rb[i] = *reinterpret_cast<const f32x4*>(bp[i] + k0);
-            }
-        };
-        const int nl = L.k / FBK;
-        if (nl > 0) {
-            lr_load(0);
-            store(0);
-            __syncthreads();
-        }
-        for (int t = 0; t < nl; ++t) {
-            if (t + 1 < nl) lr_load((t + 1) * FBK);
-            const float* As = smem + (t & 1) * (FBM + FBN) * FLD;
+        for (int kt = 0; kt < nk; ++kt) {
+            if (kt + 1 < nk) ld((kt + 1) * FBK);
+            const float* As = smem + (kt & 1) * (FBM + FBM) * FLD;
             const float* Bs = As + FBM * FLD;
 #pragma unroll
-            for (int kg = 0; kg < 2; ++kg) {
+            for (int kg = 0; kg < 2; ++kg) {               // two groups of 8 k per tile
                 f32x4 fa[NB], fb[NB];
 #pragma unroll
                 for (int i = 0; i < NB; ++i) {
-                    fa[i] = *reinterpret_cast<const f32x4*>(As + (wm + 32 * i + l31) * FLD + 8 * kg + 4 * hi);
-                    fb[i] = *reinterpret_cast<const f32x4*>(Bs + (wn + 32 * i + l31) * FLD + 8 * kg + 4 * hi);
+                    fa[i] = *reinterpret_cast<const f32x4*>(As + (t.wm + 32 * i + t.l31) * FLD + 8 * kg + 4 * t.hi);
+                    fb[i] = *reinterpret_cast<const f32x4*>(Bs + (t.wn + 32 * i + t.l31) * FLD + 8 * kg + 4 * t.hi);
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
                     for (int i = 0; i < NB; ++i)
 #pragma unroll
-                        for (int j = 0; j < NB; ++j) acc[i][j] = mfma32f(fb[i][e], fa[j][e], acc[i][j]);
+                        for (int j = 0; j < NB; ++j)       // D[n][m]: lane (m = l31, hi) ends up with n = 8 g + 4 hi + e
+                            acc[i][j] = mfma32f(fb[i][e], fa[j][e], acc[i][j]);
             }
-            if (t + 1 < nl) store((t + 1) & 1);
+            if (kt + 1 < nk) store((kt + 1) & 1);
             __syncthreads();
         }
-    }
-
-    // ---- epilogue (every option of AidGemmProblem; fp32 needs no intermediate rounding)
-    const float* stats = P.ln_stats ? P.ln_stats + 2 * (int64_t)batch * P.stride_stats : nullptr;
-    const float* bias = reinterpret_cast<const float*>(P.bias);
-    // (laid out like C, batch stride included — aid_hip.h; the batch offset was missing here until the batched DoRA test met it)
-    const float* R = P.residual ? reinterpret_cast<const float*>(P.residual) + (int64_t)batch * P.stride_c : nullptr;
-    const bool vec = !P.trans_rows && !stats && P.n % 4 == 0 &&     // whole 16-byte groups of a row: one store each
-                     (reinterpret_cast<uintptr_t>(bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0;
+    };
+    k_loop((P.k + FBK - 1) / FBK, load);
+    if constexpr (std::is_same<LRT, GemmLR>::value) {      // acc += LA LB^T: the same loop on the low-rank operands (k % 64 == 0)
+        const GemmLRDesc& L = lr.p[t.p];
+        t.rows(L.a, L.stride_a, L.lda, L.b, L.stride_b, L.ldb, sq, ap, bp);
+        auto lr_load = [&](int) {
 #pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int m = m0 + wm + 32 * j + l31;
-        if (m >= P.m) continue;
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int nb = n0 + wn + 32 * i + 8 * gq + 4 * hi;
-                if (vec) {
-                    if (nb >= P.n) continue;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * gq + e] * P.scale;
-                    // DoRA: gain on the weight rows, before every epilogue step.  (Here, as the accumulators leave their registers:
-                    // all of them scaled at once after the K loops cost the big tile a wave of occupancy.)
-                    if constexpr (std::is_same<LRT, GemmLR>::value) {
-                        const GemmLRDesc& L = lr.p[p];
-                        if (L.row_scale) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * gq + e];
-                            lr_row_scale4(v, L.row_scale, L.side, m, nb, P.n);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] *= P.scale;
-                        }
-                    }
-                    if (bias) v += *reinterpret_cast<const f32x4*>(bias + nb);
-                    const int64_t off = (int64_t)m * P.ldc + nb;
-                    if (R) v += *reinterpret_cast<const f32x4*>(R + off);
-                    *reinterpret_cast<f32x4*>(C + off) = v;
-                    continue;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = nb + e;
-                    if (n >= P.n) {                                // columns [n, round_up(n, 4)) are written with zeros (aid_hip.h)
-                        if (!P.trans_rows && n < (P.n + 3) / 4 * 4) C[(int64_t)m * P.ldc + n] = 0.f;
-                        continue;
-                    }
-                    float v = acc[i][j][4 * gq + e];
-                    if constexpr (std::is_same<LRT, GemmLR>::value) {
-                        const GemmLRDesc& L = lr.p[p];
-                        if (L.row_scale) v *= L.row_scale[L.side == 1 ? m : n];
-                    }
-                    if (stats) {                                   // folded LayerNorm: rstd (x W'^T - mean colsum) + shift
-                        if (P.ln_side == 1) v = fmaf(stats[2 * m + 1], fmaf(-stats[2 * m], P.ln_colsum[n], v), P.ln_shift[n]);
-                        else                v = fmaf(stats[2 * n + 1], fmaf(-stats[2 * n], P.ln_colsum[m], v), P.ln_shift[m]);
-                    }
-                    v *= P.scale;
-                    if (bias) v += bias[n];
-                    int64_t off;
-                    if (P.trans_rows) off = (int64_t)(m / P.trans_rows) * P.stride_c + (int64_t)n * P.ldc + m % P.trans_rows;
-                    else              off = (int64_t)m * P.ldc + n;
-                    if (R) v += R[off];
-                    C[off] = v;
-                }
+            for (int i = 0; i < RS; ++i) {
+                ra[i] = *reinterpret_cast<const f32x4*>(ap[i]);
+                rb[i] = *reinterpret_cast<const f32x4*>(bp[i]);
+                ap[i] += FBK;
+                bp[i] += FBK;
             }
+        };
+        if (L.k >= FBK) k_loop(L.k / FBK, lr_load);
     }
+    t.template epilogue<true>(acc, lr);
+}
+
+hipError_t gemm_f32_tiles(GemmGroup& g, int* tiles, bool* big) {
+    const int ncu = device_cu_count();
+    if (ncu <= 0) return hipErrorInvalidDevice;
+    *tiles = fill_tile_start(g, 128, 128);
+    *big = *tiles >= 2 * ncu;
+    if (*tiles > 0 && !*big) *tiles = fill_tile_start(g, 64, 64);
+    return hipSuccess;
 }
 
 template <typename LRT>
@@ -258,25 +146,15 @@ static void gemm_f32_run(bool big, int tiles, const GemmGroup& g, const LRT& lr,
 }
 
 hipError_t gemm_f32_launch(GemmGroup& g, hipStream_t stream, const GemmLR* lr) {
-    // big tiles only when there are enough of them to give every CU two (512 on MI355X); same arithmetic either way (the K order
-    // inside a tile does not depend on the tile size: results are bit-identical)
-    static PerDevice<int> ncu;
-    int* n = ncu.slot();
-    if (!n) return hipErrorInvalidDevice;
-    if (*n == 0) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return hipErrorInvalidDevice;
-        *n = pr.multiProcessorCount;
-    }
-    int tiles = fill_tile_start(g, 128, 128);
-    if (tiles <= 0) return hipSuccess;
-    const bool big = tiles >= 2 * *n;
-    if (!big) tiles = fill_tile_start(g, 64, 64);
+    int tiles;
+    bool big;
+    const hipError_t e = gemm_f32_tiles(g, &tiles, &big);
+    if (e != hipSuccess || tiles <= 0) return e;
     if (lr) gemm_f32_run(big, tiles, g, *lr, stream);     // the low-rank segments ride in the same launch (label: aid_gemm_f32_kernel_lr)
     else    gemm_f32_run(big, tiles, g, NoLR{}, stream);
     return hipGetLastError();
 }
+
 
 // ------------------------------------------------------------------------------------------------
 // attention

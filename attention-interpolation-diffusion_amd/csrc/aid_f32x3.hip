@@ -8,13 +8,14 @@
 // exact fp32 (3e-7) and fp16 operands (3e-4).  bf16 halves keep the fp32 exponent range (an fp16 split would not).  Inf / NaN: an
 // infinite or over-range element (|x| > 3.39e38 rounds xh to inf) gives NaN where the exact kernel gives inf.
 //
-//   aid_gemm_f32x3_kernel   C = scale * A B^T (+ bias) (+ residual): aid_gemm_f32_kernel's GemmGroup walk, staging (global ->
-//                           registers -> LDS, the next K tile's loads in flight during the MFMAs, two LDS buffers, one barrier per K
-//                           tile), edge clamping and epilogue (batches, strides, trans_rows, zeroed pad columns, 16-byte stores); no
-//                           low-rank segment and no folded LayerNorm — groups that carry either run on aid_gemm_f32_kernel (aid_abi.hip)
+//   aid_gemm_f32x3_kernel   C = scale * A B^T (+ bias) (+ residual) on the frame it shares with aid_gemm_f32_kernel (aid_gemm_f32.hpp:
+//                           GemmGroup walk, edge clamping, epilogue with batches, strides, trans_rows, zeroed pad columns and 16-byte
+//                           stores, the host's tile rule) and with that kernel's staging scheme (global -> registers -> LDS, the next
+//                           K tile's loads in flight during the MFMAs, two LDS buffers, one barrier per K tile).  Here: the split, the
+//                           four-plane LDS staging, the fragment reads and the three-term MFMA block.  No low-rank segment and no
+//                           folded LayerNorm — groups that carry either run on aid_gemm_f32_kernel (aid_abi.hip)
 //                           [attn.to_q / to_k / to_v / to_out[0], interpolation.py:613, 623-624, 666]
-#include "aid_common.hpp"
-#include "aid_kernels.hpp"
+#include "aid_gemm_f32.hpp"
 
 namespace aid {
 
@@ -55,46 +56,19 @@ __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8&
 
 template <int FBM>
 __global__ __launch_bounds__(256, 2) void aid_gemm_f32x3_kernel(const GemmGroup g) {
-    constexpr int FBN = FBM, WT = FBM / 2, NB = WT / 32, RS = FBM / 64;       // wave tile, 32-blocks per side, staging rows per thread
-    constexpr int PLANE = FBM * XLD, BUF = 4 * PLANE;                         // bf16 per plane (FBM == FBN) and per buffer
+    typedef F32Tile<FBM> Tile;
+    constexpr int NB = Tile::NB, RS = Tile::RS;
+    constexpr int PLANE = FBM * XLD, BUF = 4 * PLANE;                         // bf16 per plane and per buffer
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16* const smem = reinterpret_cast<bf16*>(smem_raw);                     // [2 buffers][Ah, Al, Bh, Bl][rows][XLD]
-    // ---- block -> (problem, batch, tile)
-    int p = 0;
-#pragma unroll
-    for (int i = 1; i < AID_GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.n_problems && (int)blockIdx.x >= g.tile_start[i]) p = i;
-    const GemmDesc& P = g.p[p];
-    int rem = blockIdx.x - g.tile_start[p];
-    const int tiles_n = (P.n + FBN - 1) / FBN, tiles_m = (P.m + FBM - 1) / FBM;
-    const int batch = rem / (tiles_m * tiles_n);
-    rem -= batch * tiles_m * tiles_n;
-    // column tiles of one row panel are neighbours in the grid: they share the A panel in L2
-    const int m0 = (rem / tiles_n) * FBM, n0 = (rem % tiles_n) * FBN;
-    const float* __restrict__ A = reinterpret_cast<const float*>(P.a) + (int64_t)batch * P.stride_a;
-    const float* __restrict__ B = reinterpret_cast<const float*>(P.b) + (int64_t)batch * P.stride_b;
-    float* __restrict__ C = reinterpret_cast<float*>(P.c) + (int64_t)batch * P.stride_c;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, hi = lane >> 5;
-    const int wm = (wave >> 1) * WT, wn = (wave & 1) * WT;
-    // staging: thread -> (row = tid / 4 [+ 64], k chunk of 8 = tid % 4); rows past the matrix are clamped (their products are never stored)
-    const int srow = tid >> 2, sq = (tid & 3) * 8;
+    const Tile t(g);
+    const GemmDesc& P = t.P;
+    const int sq = (threadIdx.x & 3) * 8;                  // staging: a thread's k chunk of 8
     const float* ap[RS];
     const float* bp[RS];
-#pragma unroll
-    for (int i = 0; i < RS; ++i) {
-        ap[i] = A + (int64_t)min(m0 + srow + 64 * i, P.m - 1) * P.lda + sq;
-        bp[i] = B + (int64_t)min(n0 + srow + 64 * i, P.n - 1) * P.ldb + sq;
-    }
-
-    f32x16 acc[NB][NB];                                    // [n block][m block]
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    t.rows(P.a, P.stride_a, P.lda, P.b, P.stride_b, P.ldb, sq, ap, bp);
+    typename Tile::Acc acc;
+    Tile::zero(acc);
 
     f32x4 ra[RS][2], rb[RS][2];
     auto load = [&](int k0) {                              // k is a multiple of 8 (aid_hip.h): a chunk is inside the row or past it
@@ -113,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void aid_gemm_f32x3_kernel(const GemmGroup 
         bf16* Bh = Ah + 2 * PLANE;
 #pragma unroll
         for (int i = 0; i < RS; ++i) {
-            const int o = (srow + 64 * i) * XLD + sq;
+            const int o = (t.srow + 64 * i) * XLD + sq;
             bf16x8 h, l;
             split8(ra[i][0], ra[i][1], h, l);
             *reinterpret_cast<bf16x8*>(Ah + o) = h;
@@ -128,17 +102,17 @@ __global__ __launch_bounds__(256, 2) void aid_gemm_f32x3_kernel(const GemmGroup 
     load(0);
     store(0);
     __syncthreads();
-    for (int t = 0; t < nk; ++t) {
-        if (t + 1 < nk) load((t + 1) * XBK);
-        const bf16* Ah = smem + (t & 1) * BUF;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) load((kt + 1) * XBK);
+        const bf16* Ah = smem + (kt & 1) * BUF;
         const bf16* Bh = Ah + 2 * PLANE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {                   // two k-steps of 16 per tile
             bf16x8 fah[NB], fal[NB], fbh[NB], fbl[NB];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
-                const int oa = (wm + 32 * i + l31) * XLD + 16 * ks + 8 * hi;
-                const int ob = (wn + 32 * i + l31) * XLD + 16 * ks + 8 * hi;
+                const int oa = (t.wm + 32 * i + t.l31) * XLD + 16 * ks + 8 * t.hi;
+                const int ob = (t.wn + 32 * i + t.l31) * XLD + 16 * ks + 8 * t.hi;
                 fah[i] = *reinterpret_cast<const bf16x8*>(Ah + oa);
                 fal[i] = *reinterpret_cast<const bf16x8*>(Ah + PLANE + oa);
                 fbh[i] = *reinterpret_cast<const bf16x8*>(Bh + ob);
@@ -158,79 +132,26 @@ __global__ __launch_bounds__(256, 2) void aid_gemm_f32x3_kernel(const GemmGroup 
 #pragma unroll
                 for (int j = 0; j < NB; ++j) acc[i][j] = mfma32(fbh[i], fah[j], acc[i][j]);
         }
-        if (t + 1 < nk) store((t + 1) & 1);
+        if (kt + 1 < nk) store((kt + 1) & 1);
         __syncthreads();
     }
-
-    // ---- epilogue: aid_gemm_f32_kernel's, without the low-rank gain and the folded LayerNorm
-    const float* bias = reinterpret_cast<const float*>(P.bias);
-    const float* R = P.residual ? reinterpret_cast<const float*>(P.residual) + (int64_t)batch * P.stride_c : nullptr;
-    const bool vec = !P.trans_rows && P.n % 4 == 0 &&              // whole 16-byte groups of a row: one store each
-                     (reinterpret_cast<uintptr_t>(bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int m = m0 + wm + 32 * j + l31;
-        if (m >= P.m) continue;
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int nb = n0 + wn + 32 * i + 8 * gq + 4 * hi;
-                if (vec) {
-                    if (nb >= P.n) continue;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * gq + e] * P.scale;
-                    if (bias) v += *reinterpret_cast<const f32x4*>(bias + nb);
-                    const int64_t off = (int64_t)m * P.ldc + nb;
-                    if (R) v += *reinterpret_cast<const f32x4*>(R + off);
-                    *reinterpret_cast<f32x4*>(C + off) = v;
-                    continue;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = nb + e;
-                    if (n >= P.n) {                                // columns [n, round_up(n, 4)) are written with zeros (aid_hip.h)
-                        if (!P.trans_rows && n < (P.n + 3) / 4 * 4) C[(int64_t)m * P.ldc + n] = 0.f;
-                        continue;
-                    }
-                    float v = acc[i][j][4 * gq + e] * P.scale;
-                    if (bias) v += bias[n];
-                    int64_t off;
-                    if (P.trans_rows) off = (int64_t)(m / P.trans_rows) * P.stride_c + (int64_t)n * P.ldc + m % P.trans_rows;
-                    else              off = (int64_t)m * P.ldc + n;
-                    if (R) v += R[off];
-                    C[off] = v;
-                }
-            }
-    }
+    t.template epilogue<false>(acc, NoLR{});               // plain groups only (aid_abi.hip): no folded LayerNorm, no gain
 }
 
 template <int FBM>
 constexpr size_t f32x3_lds_bytes() { return (size_t)2 * 4 * FBM * XLD * sizeof(bf16); }
 
 hipError_t gemm_f32x3_launch(GemmGroup& g, hipStream_t stream) {
-    // aid_gemm_f32_kernel's tile rule: big tiles only when there are enough of them to give every CU two (512 on MI355X); the K order
-    // inside a tile does not depend on the tile size, so results are bit-identical either way
-    static PerDevice<int> ncu;
     static PerDevice<int> lds_set;
-    int* n = ncu.slot();
-    if (!n) return hipErrorInvalidDevice;
-    if (*n == 0) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return hipErrorInvalidDevice;
-        *n = pr.multiProcessorCount;
-    }
-    int tiles = fill_tile_start(g, 128, 128);
-    if (tiles <= 0) return hipSuccess;
-    const bool big = tiles >= 2 * *n;
+    int tiles;
+    bool big;
+    hipError_t e = gemm_f32_tiles(g, &tiles, &big);
+    if (e != hipSuccess || tiles <= 0) return e;
     if (big) {
-        const hipError_t e = set_max_dynamic_lds(lds_set, 0, reinterpret_cast<const void*>(&aid_gemm_f32x3_kernel<128>), f32x3_lds_bytes<128>());
+        e = set_max_dynamic_lds(lds_set, 0, reinterpret_cast<const void*>(&aid_gemm_f32x3_kernel<128>), f32x3_lds_bytes<128>());
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((aid_gemm_f32x3_kernel<128>), dim3(tiles), dim3(256), f32x3_lds_bytes<128>(), stream, g);
     } else {
-        tiles = fill_tile_start(g, 64, 64);
         hipLaunchKernelGGL((aid_gemm_f32x3_kernel<64>), dim3(tiles), dim3(256), f32x3_lds_bytes<64>(), stream, g);
     }
     return hipGetLastError();

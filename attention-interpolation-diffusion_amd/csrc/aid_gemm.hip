@@ -1669,10 +1669,9 @@ static hipError_t launch_ppx(GemmGroup& g, hipStream_t stream, const GemmSide& s
     return hipGetLastError();
 }
 
-static PerDevice<int> g_num_cu;
-
-static int num_cu() {                       // CU count of the CURRENT device (cached per device)
-    int* n = g_num_cu.slot();
+int device_cu_count() {                     // CU count of the CURRENT device (cached per device); 0: it cannot be read
+    static PerDevice<int> cus;
+    int* n = cus.slot();
     if (!n) return 0;
     if (*n == 0) {
         int dev = 0;
@@ -1968,7 +1967,7 @@ hipError_t gemm_group_launch(GemmGroup& g, int dtype, hipStream_t stream, const 
                 lr->p[j - 1] = u;
             }
         }
-    const int device_cu = num_cu();
+    const int device_cu = device_cu_count();
     if (device_cu <= 0) return hipErrorInvalidDevice;
     int lr_nk = 0;
     for (int i = 0; lr && i < g.n_problems; ++i) lr_nk = lr->p[i].k / 64 > lr_nk ? lr->p[i].k / 64 : lr_nk;

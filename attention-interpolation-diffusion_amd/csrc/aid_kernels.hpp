@@ -99,6 +99,9 @@ __device__ __forceinline__ void lr_row_scale(ACC (&acc)[NB][MB], const float* __
     }
 }
 
+// CU count of the current device, read once per device; 0 when there is no device or the query fails (aid_gemm.hip)
+int device_cu_count();
+
 // fills g.tile_start (the kernels' block -> problem map) in units of bm x bn tiles and returns the tile count (aid_gemm.hip)
 int fill_tile_start(GemmGroup& g, int bm, int bn);
 
@@ -183,7 +186,7 @@ hipError_t launch_attn_plan(const AidAttnArgs& a, const AttnStep& st, hipStream_
 // d = 64 ping-pong kernel for the single-segment frames of a call (aid_attn_pp.hip); frames with more segments exit at once
 bool       attn_pp_supported(const AidAttnArgs& a);
 hipError_t attn_pp_launch(const AidAttnArgs& a, hipStream_t stream, bool multi);
-// that launch as one persistent workgroup per CU (more items than CUs, whole 8-tile trips); *n_cu: the device's CUs (<= 0: no device slot)
+// that launch as one persistent workgroup per CU (more items than CUs, whole 8-tile trips); *n_cu: the device's CUs (256 when they cannot be read)
 bool       attn_pp_persistent(const AidAttnArgs& a, bool multi, int* n_cu);
 // d = 64 kernel for TEXT keys (<= 96 keys per segment resident in LDS; aid_attn_tx.hip): whole PLAIN / INNER / OUTER calls
 bool       attn_tx_supported(const AidAttnArgs& a);

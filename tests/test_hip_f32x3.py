@@ -171,6 +171,65 @@ def test_gemm_split_is_deterministic_and_differs_from_exact():
     assert torch.equal(run("medium"), y1)
 
 
+def _int_case(case):
+    """(problem without c, C buffer shape, view of the valid C region, expected values) of a case of the test below; operands in -4 .. 4"""
+    g = torch.Generator().manual_seed(ord(case))
+    ri = lambda *sh: torch.randint(-4, 5, sh, generator=g).float()      # noqa: E731
+    prod = lambda a, b: to_np64(a) @ np.swapaxes(to_np64(b), -1, -2)      # noqa: E731  (integers below 2^53: exact)
+    if case == "a":                                        # n % 4 == 0, aligned bias and residual: 16-byte stores
+        m, n, k = 130, 132, 72
+        a, b, bias, res = ri(m, k), ri(n, k), ri(n), ri(m, n)
+        return (dict(a=a, b=b, bias=bias, residual=res, m=m, n=n, k=k, lda=k, ldb=k, ldc=n), (m, n), lambda c: c,
+                prod(a, b) + to_np64(bias) + to_np64(res))
+    if case == "b":                                        # n % 4 != 0: scalar stores, pad columns [70, 72) zero
+        m, n, k, ldc = 257, 70, 328, 72
+        a, b, bias, res = ri(m, k), ri(n, k), ri(n), torch.zeros(m, ldc)
+        res[:, :n] = ri(m, n)
+        return (dict(a=a, b=b, bias=bias, residual=res, scale=0.5, m=m, n=n, k=k, lda=k, ldb=k, ldc=ldc), (m, ldc), lambda c: c[:, :n],
+                0.5 * prod(a, b) + to_np64(bias) + to_np64(res)[:, :n])
+    if case == "c":                                        # batched, padded rows and frame gaps
+        bt, m, n, k = 3, 130, 70, 72
+        lda, ldb, ldc = k + 8, k + 16, 76
+        A, B, R = torch.full((bt, m + 2, lda), float("nan")), torch.full((bt, n + 3, ldb), float("nan")), torch.zeros(bt, m + 1, ldc)
+        a, b, res = ri(bt, m, k), ri(bt, n, k), ri(bt, m, n)
+        A[:, :m, :k], B[:, :n, :k], R[:, :m, :n] = a, b, res
+        return (dict(a=A, b=B, residual=R, m=m, n=n, k=k, lda=lda, ldb=ldb, ldc=ldc, batch=bt, stride_a=(m + 2) * lda,
+                     stride_b=(n + 3) * ldb, stride_c=(m + 1) * ldc), (bt, m + 1, ldc), lambda c: c[:, :m, :n], prod(a, b) + to_np64(res))
+    if case == "d":                                        # transposed per frame of 16 rows
+        m, n, k, tr = 48, 70, 40, 16
+        a, b = ri(m, k), ri(n, k)
+        return (dict(a=a, b=b, m=m, n=n, k=k, lda=k, ldb=k, ldc=24, stride_c=n * 24, trans_rows=tr), (m // tr, n, 24),
+                lambda c: c[:, :, :tr], prod(a, b).reshape(m // tr, tr, n).transpose(0, 2, 1))
+    m, n, k = 4096, 2048, 64                               # "e": 512 tiles of 128 x 128, the large-tile rule
+    a, b = ri(m, k), ri(n, k)
+    return dict(a=a, b=b, m=m, n=n, k=k, lda=k, ldb=k, ldc=n), (m, n), lambda c: c, prod(a, b)
+
+
+@pytest.mark.parametrize("case", ["a", "b", "c", "d", "e"])
+def test_gemm_exact_and_split_agree_bit_for_bit_on_small_integers(case):
+    """Where the split loses nothing the two kernels must agree to the bit, through every epilogue path they share
+    (csrc/aid_gemm_f32.hpp).  Operands are integers in -4 .. 4: their low bf16 halves are zero, every product and every partial sum is
+    an integer of magnitude <= 16 K <= 5248, exact in fp32 in any order; scale 0.5, integer bias and residual keep it exact.  So
+    "highest", "high" and the integer product agree exactly, inside C; around it the buffer keeps its NaN and the pad columns are +0."""
+    prob, cshape, valid, want = _int_case(case)
+    prob = {k_: v.to(DEV) if torch.is_tensor(v) else v for k_, v in prob.items()}
+    got = {}
+    for prec, variant in (("highest", "f32"), ("high", "f32x3")):
+        c = torch.full(cshape, float("nan"), device=DEV)
+        ops.gemm_nt([dict(prob, c=c, f32_precision=prec)])
+        assert ops.last_gemm_variant() == variant
+        got[prec] = c
+    assert torch.equal(valid(got["highest"]), valid(got["high"]))
+    assert np.array_equal(valid(got["high"]).cpu().numpy(), want.astype(np.float32))
+    for c in got.values():                                 # what lies around the valid region: NaN kept, pad columns zero, in both alike
+        rest = c.clone()
+        valid(rest).fill_(0.0)
+        if case in "bc":
+            assert float(rest[..., :prob["m"], 70:72].abs().max()) == 0.0
+            rest[..., :prob["m"], 70:72] = float("nan")
+        assert bool(torch.isnan(rest).sum() == rest.numel() - valid(rest).numel())
+
+
 def _exact(got, ref64, what):
     got = to_np64(got)
     assert np.isfinite(got).all() and rel_l2(got, ref64) < TOL_F32 and worst(got, ref64) < WORST_F32, (what, rel_l2(got, ref64))

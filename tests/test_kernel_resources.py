@@ -37,7 +37,7 @@ def _attn(tab):
 
 
 def test_no_kernel_spills_or_uses_scratch():
-    for obj in ("aid_attn", "aid_attn_pp", "aid_attn_tx", "aid_gemm", "aid_gemm_rs", "aid_f32", "aid_norm"):
+    for obj in ("aid_attn", "aid_attn_pp", "aid_attn_tx", "aid_gemm", "aid_gemm_rs", "aid_f32", "aid_f32x3", "aid_norm", "aid_dora"):
         for sym, r in _table(obj).items():
             assert r["scratch"] == 0 and r["spill"] == 0, (obj, sym, r)
 
@@ -115,6 +115,22 @@ def test_gemm_engines_fit_their_workgroups_per_cu():
             assert r["vgpr"] + r["agpr"] <= 256, (sym, r)         # 8 waves per CU = 2 per SIMD
         if "aid_gemm_nt_pipe_kernel" in sym:
             assert r["vgpr"] + r["agpr"] <= 128, (sym, r)         # 2 workgroups of 8 waves per CU = 4 per SIMD
+
+
+def test_fp32_gemm_kernels_keep_their_waves_per_simd():
+    """The six float32 GEMM kernels (csrc/aid_f32.hip, aid_f32x3.hip on the frame of aid_gemm_f32.hpp) at the waves per SIMD the build
+    of the commit BEFORE they shared that frame reported, when each kernel carried its own copy of the walk and the epilogue.  Registers
+    (VGPRs + AGPRs) then -> with the shared frame: exact 128 x 128 NoLR 148 -> 162, GemmLR 152 -> 162 (3 waves up to 168); exact 64 x 64
+    NoLR 56 -> 58, GemmLR 60 -> 62 (8); split 128 x 128 156 -> 156 (3 by registers; its 80 KB of LDS allow two workgroups per CU), split
+    64 x 64 78 -> 78 (6).  No SGPR spills (the epilogue works on a copy of the problem's descriptor)."""
+    want = {"aid_gemm_f32_kernelILi128ENS_4NoLRE": 3, "aid_gemm_f32_kernelILi128ENS_6GemmLRE": 3,
+            "aid_gemm_f32_kernelILi64ENS_4NoLRE": 8, "aid_gemm_f32_kernelILi64ENS_6GemmLRE": 8,
+            "aid_gemm_f32x3_kernelILi128E": 3, "aid_gemm_f32x3_kernelILi64E": 6}
+    syms = {**_table("aid_f32"), **_table("aid_f32x3")}
+    for key, occ in want.items():
+        hit = [r for s, r in syms.items() if key in s]
+        assert len(hit) == 1, key
+        assert hit[0]["occ"] >= occ and hit[0]["sgpr_spill"] == 0 and hit[0]["scratch"] == 0 and hit[0]["spill"] == 0, (key, hit[0])
 
 
 def test_row_stationary_gemm_keeps_its_rows_in_registers_without_spilling():

@@ -9,8 +9,12 @@ Per function symbol the instruction stream is kept (comments and directives drop
 paired after removing what only names the low-rank variant of a GEMM kernel: a `_lr` suffix of the kernel name and the NoLR / GemmLR
 template argument; a kernel with the segment (GemmLR anywhere in its symbol) only pairs with one that has it too.  Prints SAME or DIFF
 per pair with the line counts; for a DIFF of equal length, the number of differing lines and (--show N) the first N of them.
-usage (CPU only):  python tools/isa_diff.py old.s new.s [--show N]"""
-import argparse, re
+--mix: under every DIFF, the mnemonics whose instruction counts differ (old -> new).  A DIFF whose list holds only scalar and integer
+bookkeeping (s_load_*, s_waitcnt, s_mov_*, v_mov_*, address arithmetic) kept its arithmetic and its memory accesses; one that lists
+a v_mfma_*, v_fma_*, v_mul_*, v_add_f32, v_pk_*, v_cvt_*, global_*, ds_* or s_barrier line did not.  No list: same mix, other order
+or registers.
+usage (CPU only):  python tools/isa_diff.py old.s new.s [--show N] [--mix]"""
+import argparse, collections, re
 
 
 def key(sym):
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--show", type=int, default=0, help="print the first N differing lines of a DIFF of equal length")
+    ap.add_argument("--mix", action="store_true", help="print the per-mnemonic instruction counts that differ in a DIFF")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
     for k in sorted(set(old) | set(new)):
@@ -56,6 +61,11 @@ def main():
         print(f"DIFF     {name}  ({len(bo)} -> {len(bn)} lines" + (f", {len(pairs)} differ)" if pairs else ")"))
         for x, y in pairs[:a.show]:
             print(f"             {x}   ->   {y}")
+        if a.mix:
+            co, cn = (collections.Counter(t.split()[0] for t in b if not t.startswith(".LBB")) for b in (bo, bn))
+            for mn in sorted(set(co) | set(cn)):
+                if co[mn] != cn[mn]:
+                    print(f"             {mn:28s} {co[mn]:6d} -> {cn[mn]:6d}")
 
 
 if __name__ == "__main__":

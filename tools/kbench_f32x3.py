@@ -4,7 +4,9 @@
 
 Shapes: the SD1.5 stack at batch 3 (m = 3 S, C = 320 / 640 / 1280 / 1280: the out projection x Wo^T and the grouped q / k / V^T launch
 as aid_processor_fwd issues it), the Cc = 768 text projections (k and batched V^T of 3 x 77 tokens), and two SDXL projections.
-Prints us and TFLOP/s (2 m n k) per launch; `verdict` = split faster than exact by more than the repeats' spread."""
+Prints us and TFLOP/s (2 m n k) per launch; `verdict` = split faster than exact by more than the repeats' spread.
+The last row is a launch with a rank-64 low-rank segment (m 3072, n 640, k 640, bias + residual, as tests/test_hip_lora.py builds it):
+such a group runs the exact kernel under either setting, so both columns time aid_gemm_f32_kernel_lr."""
 import os
 import sys
 
@@ -70,6 +72,12 @@ def main():
             dict(a=e, b=wk, c=k, m=nctx * l, n=c, k=cc, lda=cc, ldb=cc, ldc=c, f32_precision=prec),
             dict(a=wv, b=e, c=vt, m=c, n=l, k=cc, lda=cc, ldb=cc, ldc=lp, batch=nctx, stride_a=0, stride_b=l * cc, stride_c=c * lp,
                  f32_precision=prec)])
+    m, n, k, r = 3072, 640, 640, 64
+    x, w, bias, res, y = rn(m, k), rn(n, k), rn(n), rn(m, n), torch.empty(m, n, device=dev)
+    u, bp = rn(m, r + 64), rn(n, r + 8)                              # padded rows: lr_lda / lr_ldb > lr_k
+    ab(f"low-rank r={r} m={m} n={n} k={k}", lambda prec: [
+        dict(a=x, b=w, c=y, bias=bias, residual=res, m=m, n=n, k=k, lda=k, ldb=k, ldc=n, f32_precision=prec,
+             lr=dict(a=u, b=bp, k=r, lda=r + 64, ldb=r + 8))])
 
 
 if __name__ == "__main__":
