@@ -18,6 +18,7 @@ from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInter
                          clear_text_kv_cache, clear_weight_caches, deactivate_aid, load_aid, load_aid_ip_adapter)
 from .attn_shim import AttnShim, AttnStackUNet, IPAdapterShim
 from . import ops, _lib, sequence, loop, dist, prior, pipelines
+from .ops import get_f32_attn_precision, set_f32_attn_precision
 from .prior import BetaPriorExplorer, BetaPriorPipeline
 from .pipelines import (DDIMSchedulerLite, InterpolationStableDiffusionPipeline,
                         InterpolationStableDiffusionXLPipeline, StackDenoiser)
@@ -28,7 +29,7 @@ __all__ = [
     "OuterInterpolatedIPAttnProcessor", "InnerInterpolatedIPAttnProcessor", "ScaleControlIPAttnProcessor",
     "HipAttnProcessor", "HipIPAdapterAttnProcessor", "load_aid", "load_aid_ip_adapter", "activate_aid", "deactivate_aid",
     "clear_text_kv_cache", "clear_weight_caches",
-    "AttnShim", "AttnStackUNet", "IPAdapterShim", "ops",
+    "AttnShim", "AttnStackUNet", "IPAdapterShim", "ops", "set_f32_attn_precision", "get_f32_attn_precision",
     "BetaPriorPipeline", "BetaPriorExplorer", "InterpolationStableDiffusionPipeline", "InterpolationStableDiffusionXLPipeline", "DDIMSchedulerLite", "StackDenoiser",
 ]
 __version__ = "0.1.0"

@@ -59,7 +59,7 @@ class AidAttnArgs(C.Structure):
         ("accumulate", C.c_int32), ("dtype", C.c_int32),
         ("softmax_scale", C.c_float), ("out_scale", C.c_float),
         ("n_plain", C.c_int32), ("q_prescaled", C.c_int32),
-        ("seg_executed", C.c_int32), ("reserved0", C.c_int32),
+        ("seg_executed", C.c_int32), ("f32_split", C.c_int32),
         ("bias", C.c_void_p), ("bias_fs", C.c_int64), ("bias_hs", C.c_int32), ("bias_rs", C.c_int32),
     ]
 
@@ -78,7 +78,7 @@ class AidProcessorArgs(C.Structure):
         ("ip", C.c_void_p), ("wk_ip", C.c_void_p), ("wv_ip", C.c_void_p), ("ip_map", C.c_void_p),
         ("ip_frame_scale", C.c_void_p), ("ip_stride", C.c_int64),
         ("n_ip", C.c_int32), ("t_ip", C.c_int32), ("ip_mode", C.c_int32), ("ip_scale", C.c_float),
-        ("ip_begin", C.c_int32), ("ip_end", C.c_int32), ("seg_executed", C.c_int32), ("reserved2", C.c_int32),
+        ("ip_begin", C.c_int32), ("ip_end", C.c_int32), ("seg_executed", C.c_int32), ("f32_attn_split", C.c_int32),
         ("ln_wq", C.c_void_p), ("ln_wk", C.c_void_p), ("ln_wv", C.c_void_p), ("ln_const", C.c_void_p),
         ("k_cached", C.c_void_p), ("vt_cached", C.c_void_p),
         ("cu_share", C.c_int32), ("f32_split", C.c_int32),

@@ -211,6 +211,7 @@ int check_processor(const AidProcessorArgs& a) {
         return AID_ERR_ARG;                            // the mask covers one key segment (aid_hip.h); the image branch has no mask to take
     if (!(a.ln_eps >= 0.f) || a.cu_share < 0 || a.cu_share > 8) return AID_ERR_ARG;
     if ((a.f32_split != 0 && a.f32_split != 1) || (a.f32_split && a.dtype != AID_DTYPE_F32)) return AID_ERR_ARG;
+    if ((a.f32_attn_split != 0 && a.f32_attn_split != 1) || (a.f32_attn_split && a.dtype != AID_DTYPE_F32)) return AID_ERR_ARG;
     if (a.ln_eps > 0.f) {
         if (!aid::layernorm_width_supported(a.c)) return AID_ERR_SHAPE;
         if ((a.ln_gamma && !aligned16(a.ln_gamma)) || (a.ln_beta && !aligned16(a.ln_beta))) return AID_ERR_SHAPE;
@@ -497,6 +498,7 @@ int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
         return AID_ERR_ARG;
     if (!a.kv_map && a.n_kv < a.n_frames) return AID_ERR_ARG;
     if (a.mode == AID_MODE_INNER && (!a.k2 || !a.vt2 || !aligned16(a.k2) || !aligned16(a.vt2))) return AID_ERR_ARG;
+    if ((a.f32_split != 0 && a.f32_split != 1) || (a.f32_split && a.dtype != AID_DTYPE_F32)) return AID_ERR_ARG;   // precision of the two products
     if (!aid::attn_head_dim_supported(a.d)) return AID_ERR_SHAPE;
     if (a.ldq % 8 || a.ldk % 8 || a.ldvt % 8 || a.ldo % 4 || a.ldvt < a.l) return AID_ERR_SHAPE;
     if (a.q_fs % 8 || a.k_fs % 8 || a.vt_fs % 8 || a.o_fs % 4) return AID_ERR_SHAPE;
@@ -737,6 +739,7 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
     at.n_plain = a.n_plain;
     at.q_prescaled = 1;
     at.seg_executed = a.seg_executed;
+    at.f32_split = a.f32_attn_split;                          // (the image branch below copies it with the rest)
     rc = aid_attn_fwd(&at, stream);
     if (rc != AID_OK) return rc;
 

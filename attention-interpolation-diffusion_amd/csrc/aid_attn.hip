@@ -1271,8 +1271,10 @@ AttnPlan plan_attn(const AidAttnArgs& a) {
     pl.n_single = a.mode == AID_MODE_PLAIN ? a.n_frames : a.n_plain + ((a.fused && a.n_frames - a.n_plain >= 2) ? 2 : 0);
     if (a.dtype == AID_DTYPE_F32) {             // float32 storage: one correctness-first kernel for every mode (aid_f32.hip)
         st->engine = AttnEngine::F32;
-        snprintf(st->label, sizeof(st->label), "aid_attn_f32<d%d,%s>", a.d, mode);
-        snprintf(pl.variant, sizeof(pl.variant), "aid_attn_f32");
+        // f32_split = 1 permits the three-term bf16 kernel (aid_f32x3.hip); what it does not run stays exact (attn_f32x3_supported)
+        st->split = a.f32_split == 1 && attn_f32x3_supported(a);
+        snprintf(st->label, sizeof(st->label), "aid_attn_f32%s<d%d,%s>", st->split ? "x3" : "", a.d, mode);
+        snprintf(pl.variant, sizeof(pl.variant), st->split ? "aid_attn_f32x3" : "aid_attn_f32");
         return pl;
     }
     const int v2 = tune(TUNE_ATTN_V2);
@@ -1337,7 +1339,7 @@ AttnPlan plan_attn(const AidAttnArgs& a) {
 
 hipError_t launch_attn_plan(const AidAttnArgs& a, const AttnStep& st, hipStream_t stream) {
     switch (st.engine) {
-        case AttnEngine::F32: return attn_f32_launch(a, stream);
+        case AttnEngine::F32: return st.split ? attn_f32x3_launch(a, stream) : attn_f32_launch(a, stream);
         case AttnEngine::Tx:  return attn_tx_launch(a, stream);
         case AttnEngine::Pp:  return attn_pp_launch(a, stream, st.share == AttnShare::All);
         case AttnEngine::Order: break;

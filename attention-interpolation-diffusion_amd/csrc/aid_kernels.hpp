@@ -161,17 +161,21 @@ hipError_t gemm_f32_launch(GemmGroup& g, hipStream_t stream, const GemmLR* lr = 
 // plain groups only: no low-rank segment, no folded LayerNorm
 hipError_t gemm_f32x3_launch(GemmGroup& g, hipStream_t stream);
 hipError_t attn_f32_launch(const AidAttnArgs& a, hipStream_t stream);
+// the same core with both products from bf16 halves (aid_f32x3.hip; AidAttnArgs.f32_split): d = 40 / 64 / 80, every mode and option
+bool       attn_f32x3_supported(const AidAttnArgs& a);
+hipError_t attn_f32x3_launch(const AidAttnArgs& a, hipStream_t stream);
 hipError_t lerp_kv_f32_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                               int end, int64_t k_fs, int64_t vt_fs, hipStream_t stream);
 
 // attention core: plan_attn picks the kernel(s) of a call and launches nothing; launch_attn_plan runs one step of the plan (aid_attn.hip)
-enum class AttnEngine { F32, Tx, Pp, Order };         // aid_f32.hip, aid_attn_tx.hip, aid_attn_pp.hip, aid_attn_kernel (program order)
+enum class AttnEngine { F32, Tx, Pp, Order };         // aid_f32.hip / aid_f32x3.hip, aid_attn_tx.hip, aid_attn_pp.hip, aid_attn_kernel (program order)
 enum class AttnShare { All = 0, Single = 1, Rest = 2 };   // what a step runs: the whole call; the frames with ONE key segment; the others
 struct AttnStep {
     AttnEngine engine = AttnEngine::Order;
     AttnShare  share = AttnShare::All;                // Pp + Single, then Order + Rest (AttnKParams.skip_single): the two launches of a split call
     int  nw = 4, qb = 1;                              // Order, the variant: waves per workgroup, 32-row query blocks per wave, software-
     bool pipe = false, res = false, bias = false;     //   pipelined loop, resident key segments, score bias (at most one differs from these)
+    bool split = false;                               // F32: the three-term bf16 kernel (aid_attn_f32x3_kernel)
     int  nqb = 0, q_iters = 1;                        // Order: workgroups per (frame, head), query blocks each works through
     char label[64] = "";                              // profile entry (AidProfileEntry.kernel)
 };

@@ -211,11 +211,16 @@ class AidDenoiseLoop:
         uncond_pass()
         self._warmed = {(which, cache_generation())}
 
+    @staticmethod
+    def _graph_key(which: str):
+        """A graph holds the kernels of the float32 matmul precision and of the attention core's precision it was captured under."""
+        from . import ops
+        return (which, ops.f32_split_code(), ops.f32_attn_split_code())
+
     def _run(self, which: str):
         if not self.use_graphs:
             return self._pass(which)
-        from . import ops
-        gk = (which, ops.f32_split_code())              # a graph holds the kernels of the float32 matmul precision it was captured under
+        gk = self._graph_key(which)
         g = self._graphs.get(gk)
         if g is None:
             cur = torch.cuda.current_stream()

@@ -100,9 +100,13 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 # ---- float32 matmul precision -----------------------------------------------------------------------------------------------
 # torch.set_float32_matmul_precision: "highest" = exact fp32 products (the default), "high" = every float32 number taken as the sum of
 # two bfloat16 numbers, three bf16 products (AidGemmProblem.f32_split, csrc/aid_f32x3.hip).  "medium" only PERMITS less precision than
-# "high"; it runs the same split.  Projections of float32 tensors only: 16-bit tensors never carry the field, the attention core's
-# products stay exact.
+# "high"; it runs the same split.  This setting covers the PROJECTIONS of float32 tensors; 16-bit tensors never carry the field.
+# The attention core's two products (K Q'^T, V^T P^T) have their own, package-level switch below (set_f32_attn_precision), which does
+# NOT follow the torch global: it defaults to "highest" (exact fp32 products, aid_attn_f32_kernel) and "high" permits the same split in
+# the core (AidAttnArgs.f32_split / AidProcessorArgs.f32_attn_split, aid_attn_f32x3_kernel).
 F32_PRECISIONS = {"highest": 0, "high": 1, "medium": 1}
+F32_ATTN_PRECISIONS = {"highest": 0, "high": 1}
+_f32_attn_precision = "highest"
 
 
 def f32_split_code(f32_precision: Optional[str] = None) -> int:
@@ -113,6 +117,29 @@ def f32_split_code(f32_precision: Optional[str] = None) -> int:
         return F32_PRECISIONS[f32_precision]
     except (KeyError, TypeError):
         raise ValueError(f"f32_precision must be None, 'highest', 'high' or 'medium'; got {f32_precision!r}") from None
+
+
+def set_f32_attn_precision(value: str) -> None:
+    """Package-level precision of the float32 attention core's two products: "highest" (exact, the default) or "high" (the core may
+    form them from bf16 halves).  Independent of ``torch.set_float32_matmul_precision``; read at every call."""
+    global _f32_attn_precision
+    if not isinstance(value, str) or value not in F32_ATTN_PRECISIONS:
+        raise ValueError(f"f32 attention precision must be 'highest' or 'high'; got {value!r}")
+    _f32_attn_precision = value
+
+
+def get_f32_attn_precision() -> str:
+    return _f32_attn_precision
+
+
+def f32_attn_split_code(value: Optional[str] = None) -> int:
+    """AidAttnArgs.f32_split / AidProcessorArgs.f32_attn_split of a float32 launch: ``None`` reads the package setting now."""
+    if value is None:
+        value = _f32_attn_precision
+    try:
+        return F32_ATTN_PRECISIONS[value]
+    except (KeyError, TypeError):
+        raise ValueError(f"f32_attn_precision must be None, 'highest' or 'high'; got {value!r}") from None
 
 
 # ---- scratch memory --------------------------------------------------------------------------------------------------------
@@ -472,11 +499,15 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, *, 
              accumulate: bool = False, out_scale: float = 1.0,
              frame_scale: Optional[torch.Tensor] = None, kv_map: Optional[torch.Tensor] = None,
              softmax_scale: Optional[float] = None, n_plain: int = 0, seg_executed: int = 0,
-             q_prescaled: bool = False, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+             q_prescaled: bool = False, bias: Optional[torch.Tensor] = None,
+             f32_attn_precision: Optional[str] = None) -> torch.Tensor:
     """Interpolated attention core (see AidAttnArgs in include/aid_hip.h).
     q [N, S, C], k [F, L, C], vt [F, C, Lp] contiguous; coef / frame_scale fp32 device [N].  ``bias``: additive score bias
-    (diffusers' prepared attention_mask, ``score_bias_layout``); not with ``fused``."""
+    (diffusers' prepared attention_mask, ``score_bias_layout``); not with ``fused``.
+    ``f32_attn_precision``: float32 tensors only — the precision of the two products (AidAttnArgs.f32_split), None = the package
+    setting at call time (``f32_attn_split_code``)."""
     lib = _lib.load()
+    attn_split = f32_attn_split_code(f32_attn_precision)    # (a bad value raises whatever the dtype)
     _require_gpu(q, k, vt, out, coef, frame_scale, kv_map, bias)
     dt = _dtype_code(q)
     if _dtype_code(k) != dt or _dtype_code(vt) != dt:
@@ -522,6 +553,8 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, *, 
         a.bias = bias.data_ptr()
         a.bias_fs, a.bias_hs, a.bias_rs = score_bias_layout(bias, n, heads, s, l, q.dtype)
     a.q_prescaled = int(bool(q_prescaled))              # q already holds q * softmax_scale * log2(e) (the processor path's q projection)
+    if dt == DTYPE_F32:
+        a.f32_split = attn_split
     with _on(q.device):
         _lib.check(lib.aid_attn_fwd(C.byref(a), _stream()), "aid_attn_fwd")
     return out
@@ -557,7 +590,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   residual: Optional[torch.Tensor] = None, seg_executed: int = 0,
                   ip: Optional[dict] = None, ln_folded: Optional[tuple] = None,
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                  attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None) -> torch.Tensor:
+                  attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None,
+                  f32_attn_precision: Optional[str] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -577,9 +611,12 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``kv_cached`` (the cached keys must already hold the adapter term).  ``lora.gains`` (DoRA, AidProcessorArgs.lora_gain_*): the
     fp32 row gain of each projection's adapter, or None.
     ``f32_precision``: float32 tensors only — the precision of every projection GEMM of the call (AidProcessorArgs.f32_split), None =
-    ``torch.get_float32_matmul_precision()`` at call time; the attention core stays exact."""
+    ``torch.get_float32_matmul_precision()`` at call time.
+    ``f32_attn_precision``: float32 tensors only — the precision of the attention core's two products in every attention launch of
+    the call (AidProcessorArgs.f32_attn_split), None = the package setting at call time (``f32_attn_split_code``)."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
+    attn_split = f32_attn_split_code(f32_attn_precision)
     ipt = ip or {}
     dev = _require_gpu(x, ctx, wq, wk, wv, wo, bo, coef, ctx_map, out, residual, attn_bias, *(ln[:2] if ln else ()),
                        ipt.get("tokens"), ipt.get("wk"), ipt.get("wv"), ipt.get("map"), ipt.get("frame_scale"))
@@ -684,6 +721,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     a.cu_share = current_cu_share()
     if dt == DTYPE_F32:
         a.f32_split = split
+        a.f32_attn_split = attn_split
     nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):
         if nbytes == 0:

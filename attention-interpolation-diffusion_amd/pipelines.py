@@ -202,8 +202,9 @@ class _PassGraphs:
     @staticmethod
     def _key(key):
         """A captured pass holds the kernels of the float32 matmul precision it was captured under (the processors read
-        ``torch.get_float32_matmul_precision()`` per call): a change of the global re-captures instead of replaying stale graphs."""
-        return (key, ops.f32_split_code())
+        ``torch.get_float32_matmul_precision()`` per call) and of the attention core's precision (``ops.set_f32_attn_precision``): a
+        change of either re-captures instead of replaying stale graphs, changing it back replays the old ones."""
+        return (key, ops.f32_split_code(), ops.f32_attn_split_code())
 
     def run(self, key, fn: Callable, **inputs: torch.Tensor):
         if not self.enabled:

@@ -234,7 +234,16 @@ typedef struct AidAttnArgs {
     int32_t seg_executed;        /* profiling accounting: (frame, key segment) passes this launch really runs —  */
                                  /* fused END-POINT frames and coefficient-0/1 sides run fewer than the          */
                                  /* algorithmic count; 0 = unknown (reported equal to the algorithmic count)     */
-    int32_t reserved0;
+    /* float32 precision of the two products of the core (AID_DTYPE_F32 only).  This is the field that was `reserved0`, which callers  */
+    /* left zero: layout and ABI version are unchanged.  0 (a zeroed struct): exact fp32 products on v_mfma_f32_32x32x2_f32.            */
+    /* 1 ("high"): the launch MAY form K Q'^T and V^T P^T from bfloat16 halves — the arithmetic of AidGemmProblem.f32_split,            */
+    /*     Xh = bf16_rne(X),  Xl = bf16_rne(X - float(Xh)),   A B ~= Al Bh + Ah Bl + Ah Bh   (three v_mfma_f32_32x32x16_bf16, fp32 sums) */
+    /* on Q' = Q * softmax_scale * log2(e), K, V^T and the unnormalised probabilities P; the softmax itself (maximum, exp2, row sum,    */
+    /* rescale) stays unrounded fp32.  A score is then good to ~2^-16 of |q| |k| (not of the score): ~6e-6 - 8e-6 rel-L2 of the fp64     */
+    /* output instead of ~3e-7.  A permission, never an error: a shape the split kernel does not run (or does not win on) stays on the   */
+    /* exact kernel; aid_last_attn_variant() says which ran ("aid_attn_f32x3" / "aid_attn_f32").  Needs no workspace.  An infinite or    */
+    /* over-range element gives NaN where the exact kernel gives inf.  AID_ERR_ARG: a value outside {0, 1}; non-zero with a 16-bit dtype. */
+    int32_t f32_split;
     /* ABI v8 — additive score bias (NULL: none): diffusers' attention_mask after Attention.prepare_attention_mask, which every  */
     /* reference processor hands to get_attention_scores (interpolation.py:115-117, 604-606, 651, 738-739, 787):              */
     /*     scores = softmax_scale * Q K^T + bias        (baddbmm(attention_mask, q, k^T, beta = 1, alpha = scale))              */
@@ -321,7 +330,10 @@ typedef struct AidProcessorArgs {
     float   ip_scale;
     int32_t ip_begin, ip_end;    /* AID_IP_SAME: image rows of the end-point frames           */
     int32_t seg_executed;        /* accounting, see AidAttnArgs.seg_executed (text launch only) */
-    int32_t reserved2;           /* (v6 / v7: kv_cached_lt, a tile-padded layout of the cached keys that no kernel needed; removed in v8) */
+    /* float32 precision of the attention core's two products: AidAttnArgs.f32_split, same values, same errors, copied into every     */
+    /* attention launch of the call (text branch, image branch).  Independent of f32_split below (the projections).  This is the slot  */
+    /* that was reserved2 (v6 / v7: kv_cached_lt, removed in v8), which callers left zero: zero = exact, as before.                    */
+    int32_t f32_attn_split;
     /* ---- folded LayerNorm (ln_eps > 0 and ln_wq != NULL): the call runs aid_ln_stats on x instead of aid_layernorm and  */
     /* projects x with the folded weights (aid_ln_fold of wq / wk / wv with ln_gamma / ln_beta; wk / wv only for           */
     /* self-attention, a cross-attention ctx is not normalised).  ln_const: fp32 [6, c] = colsum_q, shift_q, colsum_k,     */
@@ -340,7 +352,7 @@ typedef struct AidProcessorArgs {
     int32_t      cu_share;       /* ABI v7: see AidGemmProblem.cu_share — handed to every GEMM launch of the call            */
     /* float32 matmul precision of every projection GEMM the call launches (q / k / v / out, the image-token k / v, the LoRA down     */
     /* projections): AidGemmProblem.f32_split, same values, same errors (the field that was reserved1: zero = exact, as before).      */
-    /* The attention core's two products stay exact.                                                                                   */
+    /* The attention core's two products have their own switch: f32_attn_split above.                                                  */
     int32_t      f32_split;
     /* ABI v8: additive score bias of the text attention (attention_mask), see AidAttnArgs.bias; not with `fused`, not with `ip` */
     const void*  attn_bias;
