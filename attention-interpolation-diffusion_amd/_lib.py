@@ -20,10 +20,11 @@ DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 0, 1, 2
 MODE_PLAIN, MODE_INNER, MODE_OUTER = 0, 1, 2
 GEMM_MAX_PROBLEMS = 6
 IP_NONE, IP_SAME, IP_PLAIN = 0, 1, 2
+IP_MAX_SEGMENTS = 8
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
-    "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_processor_workspace_bytes", "aid_processor_fwd",
+    "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -61,6 +62,25 @@ class AidAttnArgs(C.Structure):
         ("n_plain", C.c_int32), ("q_prescaled", C.c_int32),
         ("seg_executed", C.c_int32), ("f32_split", C.c_int32),
         ("bias", C.c_void_p), ("bias_fs", C.c_int64), ("bias_hs", C.c_int32), ("bias_rs", C.c_int32),
+    ]
+
+
+class AidIpSegment(C.Structure):
+    _fields_ = [
+        ("k", C.c_void_p), ("vt", C.c_void_p), ("row_weight", C.c_void_p),
+        ("k_fs", C.c_int64), ("vt_fs", C.c_int64),
+        ("t", C.c_int32), ("ldvt", C.c_int32), ("n_rows", C.c_int32), ("scale", C.c_float),
+    ]
+
+
+class AidIpAttnArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("out", C.c_void_p), ("segments", C.c_void_p),
+        ("n_segments", C.c_int32),
+        ("n_frames", C.c_int32), ("s", C.c_int32), ("heads", C.c_int32), ("d", C.c_int32),
+        ("ldq", C.c_int32), ("ldo", C.c_int32), ("dtype", C.c_int32),
+        ("q_fs", C.c_int64), ("o_fs", C.c_int64),
+        ("softmax_scale", C.c_float), ("q_prescaled", C.c_int32),
     ]
 
 
@@ -149,6 +169,8 @@ def bind(path: str) -> C.CDLL:
                                 C.c_int32, C.c_void_p]
     lib.aid_attn_fwd.restype = C.c_int
     lib.aid_attn_fwd.argtypes = [C.POINTER(AidAttnArgs), C.c_void_p]
+    lib.aid_ip_attn_fwd.restype = C.c_int
+    lib.aid_ip_attn_fwd.argtypes = [C.POINTER(AidIpAttnArgs), C.c_void_p]
     lib.aid_lerp_kv.restype = C.c_int
     lib.aid_lerp_kv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
@@ -156,6 +178,8 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs)]
     lib.aid_processor_fwd.restype = C.c_int
     lib.aid_processor_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.c_void_p]
+    lib.aid_processor_ip_fwd.restype = C.c_int
+    lib.aid_processor_ip_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.c_void_p, C.c_int32, C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

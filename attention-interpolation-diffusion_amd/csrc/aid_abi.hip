@@ -177,6 +177,18 @@ Carve carve(const AidProcessorArgs& a) {
     return c;
 }
 
+// image segments of aid_ip_attn_fwd / aid_processor_ip_fwd (aid_hip.h): any count >= 1 here, the callers bound it
+int check_ip_segments(const AidIpSegment* segs, int n, int n_frames) {
+    if (!segs || n < 1) return AID_ERR_ARG;
+    for (int g = 0; g < n; ++g) {
+        const AidIpSegment& s = segs[g];
+        if (!s.k || !s.vt || s.t < 1 || (s.n_rows != 1 && s.n_rows != n_frames)) return AID_ERR_ARG;
+        if (s.ldvt % 8 || s.ldvt < s.t || s.k_fs % 8 || s.vt_fs % 8 || s.k_fs < 0 || s.vt_fs < 0) return AID_ERR_SHAPE;
+        if (!aligned16(s.k) || !aligned16(s.vt) || (s.row_weight && !aligned4(s.row_weight))) return AID_ERR_SHAPE;
+    }
+    return AID_OK;
+}
+
 int check_processor(const AidProcessorArgs& a) {
     if (!a.x || !a.wq || !a.wk || !a.wv || !a.wo || !a.y) return AID_ERR_ARG;
     if (!dtype_ok(a.dtype)) return AID_ERR_DTYPE;
@@ -537,6 +549,37 @@ int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_attn_fwd");
 }
 
+int aid_ip_attn_fwd(const AidIpAttnArgs* args, void* stream) {
+    if (!args) return AID_ERR_ARG;
+    const AidIpAttnArgs& a = *args;
+    if (!a.q || !a.out || !a.segments) return AID_ERR_ARG;
+    if (a.n_segments < 1 || a.n_segments > AID_IP_MAX_SEGMENTS) return AID_ERR_ARG;
+    if (a.n_frames < 1 || a.s < 1 || a.heads < 1 || a.d < 1) return AID_ERR_ARG;
+    if (!a.q_prescaled && !(a.softmax_scale > 0.f)) return AID_ERR_ARG;
+    if (!dtype16(a.dtype)) return AID_ERR_DTYPE;            // float32 storage has no segment form
+    if (!aid::attn_head_dim_supported(a.d)) return AID_ERR_SHAPE;
+    if (a.ldq % 8 || a.ldo % 8 || a.q_fs % 8 || a.o_fs % 8 || a.q_fs < 0 || a.o_fs < 0) return AID_ERR_SHAPE;
+    if ((int64_t)a.ldq < (int64_t)a.heads * a.d || (int64_t)a.ldo < (int64_t)a.heads * a.d) return AID_ERR_SHAPE;
+    if (!aligned16(a.q) || !aligned16(a.out)) return AID_ERR_SHAPE;
+    const int rc = check_ip_segments(a.segments, a.n_segments, a.n_frames);
+    if (rc != AID_OK) return rc;
+    hipError_t e;
+    {
+        // work: 4 s t c per (frame, segment); traffic: q read, out read and written, every segment's K / V^T rows once
+        const double c = (double)a.heads * a.d;
+        double keys = 0, kv = 0;
+        for (int g = 0; g < a.n_segments; ++g) {
+            keys += a.segments[g].t;
+            kv += 2.0 * a.segments[g].n_rows * (double)a.segments[g].t * c;
+        }
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_ip_attn<%s,d%d,g%d>", dtype_name(a.dtype), a.d, a.n_segments);
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 4.0 * a.n_frames * a.s * keys * c, 2.0 * (3.0 * a.n_frames * a.s * c + kv));
+        e = aid::ip_attn_launch(a, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_ip_attn_fwd");
+}
+
 static int lerp_kv_impl(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int32_t n_frames,
                         int32_t begin, int32_t end, int64_t k_fs, int64_t vt_fs, int32_t dtype, void* stream,
                         int n_interior) {
@@ -569,11 +612,20 @@ size_t aid_processor_workspace_bytes(const AidProcessorArgs* args) {
     return carve(*args).total;
 }
 
-int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
+int aid_processor_fwd(const AidProcessorArgs* args, void* stream) { return aid_processor_ip_fwd(args, nullptr, 0, stream); }
+
+int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, void* stream) {
     if (!args) return AID_ERR_ARG;
     const AidProcessorArgs& a = *args;
     int rc = check_processor(a);
     if (rc != AID_OK) return rc;
+    if (n_ip_segs < 0 || (n_ip_segs == 0 && ip_segs)) return AID_ERR_ARG;
+    if (n_ip_segs > 0) {                               // image segments: a cross-attention PLAIN call without the ip_* branch, 16-bit
+        if (!a.ctx || a.mode != AID_MODE_PLAIN || a.ip) return AID_ERR_ARG;
+        if (!dtype16(a.dtype)) return AID_ERR_DTYPE;
+        rc = check_ip_segments(ip_segs, n_ip_segs, a.n_frames);
+        if (rc != AID_OK) return rc;
+    }
     const Carve cv = carve(a);
     if (!a.workspace || a.workspace_bytes < cv.total || !aligned16(a.workspace)) return AID_ERR_WORKSPACE;
     char* ws = static_cast<char*>(a.workspace);
@@ -759,6 +811,23 @@ int aid_processor_fwd(const AidProcessorArgs* args, void* stream) {
             ai.mode = AID_MODE_PLAIN; ai.fused = 0; ai.coef = nullptr; ai.begin = 0; ai.end = 0; ai.n_plain = 0;
         }
         rc = aid_attn_fwd(&ai, stream);
+        if (rc != AID_OK) return rc;
+    }
+
+    // 2c. image segments (several IP-Adapters / regional masks): all of them in one launch per AID_IP_MAX_SEGMENTS, into o
+    for (int g0 = 0; g0 < n_ip_segs; g0 += AID_IP_MAX_SEGMENTS) {
+        AidIpAttnArgs is;
+        memset(&is, 0, sizeof(is));
+        is.q = q; is.out = o;
+        is.segments = ip_segs + g0;
+        is.n_segments = n_ip_segs - g0 < AID_IP_MAX_SEGMENTS ? n_ip_segs - g0 : AID_IP_MAX_SEGMENTS;
+        is.n_frames = a.n_frames; is.s = a.s; is.heads = a.heads; is.d = d;
+        is.ldq = a.c; is.ldo = a.c;
+        is.q_fs = (int64_t)a.s * a.c; is.o_fs = (int64_t)a.s * a.c;
+        is.dtype = a.dtype;
+        is.softmax_scale = 1.0f / sqrtf((float)d);
+        is.q_prescaled = 1;
+        rc = aid_ip_attn_fwd(&is, stream);
         if (rc != AID_OK) return rc;
     }
 

@@ -196,6 +196,8 @@ bool       attn_pp_persistent(const AidAttnArgs& a, bool multi, int* n_cu);
 bool       attn_tx_supported(const AidAttnArgs& a);
 hipError_t attn_tx_launch(const AidAttnArgs& a, hipStream_t stream);
 bool       attn_head_dim_supported(int d);
+// IP-Adapter image segments accumulated into `out` in one launch (aid_attn_ip.hip; aid_ip_attn_fwd): 16-bit dtypes, arguments checked by the caller
+hipError_t ip_attn_launch(const AidIpAttnArgs& a, hipStream_t stream);
 hipError_t lerp_kv_launch(const void* k, const void* vt, void* k2, void* vt2, const float* coef, int n_frames, int begin,
                           int end, int64_t k_fs, int64_t vt_fs, int dtype, hipStream_t stream);
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,

@@ -16,8 +16,8 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, IP_NONE, IP_PLAIN, IP_SAME, MODE_INNER, MODE_OUTER, MODE_PLAIN, AidAttnArgs,
-                   AidGemmProblem, AidProcessorArgs)
+from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME, MODE_INNER, MODE_OUTER, MODE_PLAIN,
+                   AidAttnArgs, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
 IP_MODES = {"same": IP_SAME, "plain": IP_PLAIN}
@@ -560,6 +560,64 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, *, 
     return out
 
 
+def _ip_segment_array(segments: Sequence[dict], n: int, s: int, c: int, dtype: torch.dtype):
+    """The host array of AidIpSegment for ``segments`` (checked against a [n, s, c] query tensor of ``dtype``)."""
+    if dtype == torch.float32:
+        raise NotImplementedError("several IP-Adapters per layer / ip_adapter_masks (the image-segment form) are implemented for "
+                                  "float16 / bfloat16 storage; float32 storage runs one unmasked adapter per layer")
+    arr = (AidIpSegment * len(segments))()
+    for g, seg in enumerate(segments):
+        k, vt, rw = seg["k"], seg["vt"], seg.get("row_weight")
+        _require_gpu(k, vt, rw)
+        if k.dtype != dtype or vt.dtype != dtype:
+            raise TypeError(f"image keys / values must have the activation dtype ({dtype})")
+        if k.ndim != 3 or vt.ndim != 3 or not k.is_contiguous() or not vt.is_contiguous():
+            raise ValueError("an image segment is (k [R, T, C], vt [R, C, Tp]) as project_kv returns them")
+        rows, t = k.shape[0], k.shape[1]
+        if rows not in (1, n) or vt.shape[0] != rows or k.shape[2] != c or vt.shape[1] != c or t < 1 or vt.shape[2] < t or vt.shape[2] % 8:
+            raise ValueError(f"image segment {g}: k {tuple(k.shape)} / vt {tuple(vt.shape)} do not fit {n} frames of width {c} with t = {t}")
+        if rw is not None and (rw.dtype != torch.float32 or rw.numel() != s or not rw.is_contiguous()):
+            raise ValueError(f"image segment {g}: row_weight must be a contiguous float32 tensor with one entry per query row ({s})")
+        e = arr[g]
+        e.k, e.vt, e.row_weight = k.data_ptr(), vt.data_ptr(), _ptr(rw)
+        e.k_fs, e.vt_fs = k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2]
+        e.t, e.ldvt, e.n_rows = t, vt.shape[2], rows
+        e.scale = float(seg.get("scale", 1.0))
+    return arr
+
+
+def ip_attn_accumulate(q: torch.Tensor, out: torch.Tensor, segments: Sequence[dict], heads: int, *,
+                       softmax_scale: Optional[float] = None, q_prescaled: bool = False) -> torch.Tensor:
+    """``out += sum_g scale_g * w_g[row] * softmax(q K_g^T * softmax_scale) V_g`` over image-key segments, one launch per
+    ``IP_MAX_SEGMENTS`` segments (``aid_ip_attn_fwd``; fp32 accumulation, one rounding per launch).  q / out [N, S, C] contiguous,
+    float16 / bfloat16; a segment is dict(k=[R, T, C], vt=[R, C, Tp] (``project_kv``; R = N or 1 = shared by all frames), scale=float,
+    row_weight=None | float32 [S])."""
+    lib = _lib.load()
+    dev = _require_gpu(q, out)
+    if q.dtype != out.dtype or q.shape != out.shape or q.ndim != 3 or not q.is_contiguous() or not out.is_contiguous():
+        raise ValueError("q and out must be contiguous [N, S, C] tensors of one dtype")
+    n, s, c = q.shape
+    if heads < 1 or c % heads:
+        raise ValueError(f"{c} channels do not split into {heads} heads")
+    segments = list(segments)
+    arr = _ip_segment_array(segments, n, s, c, q.dtype)
+    d = c // heads
+    base = C.addressof(arr) if len(segments) else 0
+    for g0 in range(0, len(segments), IP_MAX_SEGMENTS):
+        a = AidIpAttnArgs()
+        a.q, a.out = q.data_ptr(), out.data_ptr()
+        a.segments = base + g0 * C.sizeof(AidIpSegment)
+        a.n_segments = min(IP_MAX_SEGMENTS, len(segments) - g0)
+        a.n_frames, a.s, a.heads, a.d = n, s, heads, d
+        a.ldq, a.ldo, a.q_fs, a.o_fs = c, c, s * c, s * c
+        a.dtype = _dtype_code(q)
+        a.softmax_scale = float(d ** -0.5 if softmax_scale is None else softmax_scale)
+        a.q_prescaled = int(bool(q_prescaled))
+        with _on(dev):
+            _lib.check(lib.aid_ip_attn_fwd(C.byref(a), _stream()), "aid_ip_attn_fwd")
+    return out
+
+
 def set_tuning(name: str, value: int = -1) -> None:
     """Development knob of the library (``aid_set_tuning``): ``value < 0`` hands the choice back to the launch heuristics."""
     _lib.check(_lib.load().aid_set_tuning(name.encode(), int(value)), f"aid_set_tuning({name})")
@@ -591,7 +649,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   ip: Optional[dict] = None, ln_folded: Optional[tuple] = None,
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None,
-                  f32_attn_precision: Optional[str] = None) -> torch.Tensor:
+                  f32_attn_precision: Optional[str] = None, ip_segments: Optional[Sequence[dict]] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -613,7 +671,10 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``f32_precision``: float32 tensors only — the precision of every projection GEMM of the call (AidProcessorArgs.f32_split), None =
     ``torch.get_float32_matmul_precision()`` at call time.
     ``f32_attn_precision``: float32 tensors only — the precision of the attention core's two products in every attention launch of
-    the call (AidProcessorArgs.f32_attn_split), None = the package setting at call time (``f32_attn_split_code``)."""
+    the call (AidProcessorArgs.f32_attn_split), None = the package setting at call time (``f32_attn_split_code``).
+    ``ip_segments``: image-key segments (``ip_attn_accumulate``'s dicts; ``aid_processor_ip_fwd``) added to the attention output in
+    one launch after the text attention — several IP-Adapters per layer, regional masks as ``row_weight``.  A cross-attention
+    ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
     attn_split = f32_attn_split_code(f32_attn_precision)
@@ -718,6 +779,11 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                 if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() != c or not r_:
                     raise ValueError("DoRA gains are contiguous float32 [C] tensors of projections that have a rank")
         a.lora_gain_q, a.lora_gain_k, a.lora_gain_v, a.lora_gain_o = (_ptr(t_) for t_ in gains)
+    seg_arr = None
+    if ip_segments:
+        if ctx is None or mode != "plain" or ip is not None:
+            raise ValueError("ip_segments belong to a cross-attention mode='plain' call without the `ip` branch")
+        seg_arr = _ip_segment_array(list(ip_segments), n, s, c, x.dtype)
     a.cu_share = current_cu_share()
     if dt == DTYPE_F32:
         a.f32_split = split
@@ -731,5 +797,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
             raise RuntimeError("aid_processor_workspace_bytes returned 0")
         ws = workspace(nbytes, dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
+        if seg_arr is not None:
+            _lib.check(lib.aid_processor_ip_fwd(C.byref(a), C.addressof(seg_arr), len(seg_arr), _stream()), "aid_processor_ip_fwd")
+        else:
+            _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
     return out

@@ -21,12 +21,14 @@ Differences from the reference that are deliberate and documented:
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import lora, ops
@@ -343,6 +345,7 @@ def clear_weight_caches() -> None:
     before the call still read the old derived tensors and must be re-captured."""
     _KV_CACHE.clear()
     _FOLD_CACHE.clear()
+    _IP_KV_CACHE.clear()
     lora.clear()
     _CACHE_GEN[0] += 1
 
@@ -603,15 +606,145 @@ def _split_ip(encoder_hidden_states, num_tokens):
 
 def _ip_token_rows(ip_list) -> torch.Tensor:
     """ip_hidden_states[0] as [R, E*T, Cc]: a 4-D [R, E, T, Cc] input folds E into the token axis
-    (head_to_batch_dim on 4-D tensors, interpolation.py:334-341)."""
-    if len(ip_list) != 1:
-        raise NotImplementedError("one IP-Adapter per layer (the reference reads to_k_ip[0] / scale[0] only)")
+    (head_to_batch_dim on 4-D tensors, interpolation.py:334-341).  With several adapters loaded the ACTIVATED reference processors
+    read adapter 0 only (``ip_hidden_states[0]``, ``to_k_ip[0]``, ``scale[0]``: interpolation.py:330-331, 365, 502-503, 530), and so
+    do the callers of this function; the de-activated path (HipIPAdapterAttnProcessor) runs every adapter."""
     rows = ip_list[0]
     if rows.ndim == 4:
         rows = rows.reshape(rows.shape[0], rows.shape[1] * rows.shape[2], rows.shape[3])
     if rows.ndim != 3:
         raise RuntimeError(f"image embeddings must be [R, T, Cc] or [R, E, T, Cc], got {tuple(rows.shape)}")
     return rows.contiguous()
+
+
+# Image keys / values and regional row weights of the SEGMENT form (several adapters per layer, ip_adapter_masks, attention_mask next
+# to image embeddings).  The image embeddings do not change over the denoising loop, so K = to_k_ip[j](tokens), V^T = Wv tokens^T are
+# projected once per (adapter[, image]) and kept the way ``_text_kv`` keeps the text keys: keyed on (data_ptr, _version) of the
+# caller's embedding tensor and of the two weights, dropped when the embedding tensor dies (weakref) and by
+# ``clear_weight_caches()``.  The row weights of a mask are kept per (mask tensor, image, S) in the same dictionary.
+_IP_KV_CACHE: Dict[Tuple, Tuple] = {}
+
+
+def _ip_cached(kind: str, versions: Tuple, rest: Tuple, owner: torch.Tensor, build):
+    """``build()`` once per (kind, versions, rest) while ``owner`` lives; ``versions`` = ``_vkey`` of the tensors it is built from — not
+    cached where one cannot be read (None).  A miss drops what was built from the same ``owner`` and the same ``rest`` at other
+    versions; ``rest`` therefore names everything else the value depends on (the layer's weights: every IP layer of a UNet gets the
+    SAME embedding tensors and has its own ``to_k_ip`` / ``to_v_ip``)."""
+    if not TEXT_KV_CACHE or any(v is None for v in versions):
+        return build()
+    key = (kind, versions, rest)
+    hit = _IP_KV_CACHE.get(key)
+    if hit is not None and hit[1]() is not owner:
+        hit = None
+    if hit is None:
+        _CACHE_GEN[0] += 1
+        for old in [k for k, v in _IP_KV_CACHE.items() if k[0] == kind and k[2] == rest and v[1]() is owner]:
+            _IP_KV_CACHE.pop(old, None)
+
+        def _drop(_ref, key=key):
+            _IP_KV_CACHE.pop(key, None)
+        hit = (build(), weakref.ref(owner, _drop))
+        _IP_KV_CACHE[key] = hit
+    return hit[0]
+
+
+def _ip_segment_kv(ip_state: torch.Tensor, image: Optional[int], n: int, wk: torch.Tensor, wv: torch.Tensor):
+    """(k [n, T', C], vt [n, C, T'p]) of one adapter's tokens — all ``E T`` tokens of a frame as ONE key segment (image None:
+    diffusers' ``view(batch, -1, heads, head_dim)``) or those of image ``image`` of a 4-D state."""
+    def build():
+        tok = ip_state if image is None else ip_state[:, image]
+        if tok.shape[0] % n:
+            raise RuntimeError(f"{tok.shape[0]} image-embedding rows do not fold into a batch of {n}")
+        tok = tok.reshape(n, -1, tok.shape[-1]).contiguous()
+        return ops.project_kv(tok, wk, wv)
+    return _ip_cached("kv", (_vkey(ip_state), _vkey(wk), _vkey(wv)),
+                      (tuple(ip_state.shape), ip_state.dtype, ip_state.device, image, n, wk.data_ptr(), wv.data_ptr()), ip_state, build)
+
+
+def mask_row_weights(mask: torch.Tensor, s: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """diffusers' ``IPAdapterMaskProcessor.downsample(mask, batch, S, C)[0, :, 0]`` (0.27 - 0.31, restated) for one image's mask
+    ``[1, H, W]``: bicubic resize to ``(mh, mw)`` with ``mh = int(sqrt(S / (W / H)))`` (+ 1 if it does not divide S), ``mw = S // mh``,
+    flattened, zero-padded or truncated to S, cast to the activation dtype — as float32 [S] on ``device`` for the kernel."""
+    o_h, o_w = mask.shape[1], mask.shape[2]
+    ratio = o_w / o_h
+    mh = int(math.sqrt(s / ratio))
+    mh = int(mh) + int((s % int(mh)) != 0)
+    mw = s // mh
+    m = F.interpolate(mask.to(device).unsqueeze(0), size=(mh, mw), mode="bicubic").squeeze(0)
+    m = m.reshape(m.shape[0], -1)[0]
+    if m.numel() < s:
+        m = F.pad(m, (0, s - m.numel()), value=0.0)
+    elif m.numel() > s:
+        m = m[:s]
+    return m.to(dtype).to(torch.float32).contiguous()
+
+
+def _ip_row_weight(mask: torch.Tensor, image: int, s: int, dtype: torch.dtype, device) -> torch.Tensor:
+    return _ip_cached("rw", (_vkey(mask),), (tuple(mask.shape), mask.dtype, mask.device, image, s, dtype, device), mask,
+                      lambda: mask_row_weights(mask[:, image], s, dtype, device))
+
+
+def _check_ip_masks(ip_adapter_masks, scales, ip_states):
+    """diffusers' checks of ``ip_adapter_masks`` (IPAdapterAttnProcessor2_0.__call__), with its ValueErrors; returns the list."""
+    if not isinstance(ip_adapter_masks, list):
+        # (backward compatibility in diffusers: one tensor [adapters, images, H, W] is split along dim 0)
+        ip_adapter_masks = list(ip_adapter_masks.unsqueeze(1))
+    if not (len(ip_adapter_masks) == len(scales) == len(ip_states)):
+        raise ValueError(f"Length of ip_adapter_masks array ({len(ip_adapter_masks)}) must match length of self.scale array "
+                         f"({len(scales)}) and number of ip_hidden_states ({len(ip_states)})")
+    for index, (mask, scale, ip_state) in enumerate(zip(ip_adapter_masks, scales, ip_states)):
+        if mask is None:
+            continue
+        if not isinstance(mask, torch.Tensor) or mask.ndim != 4:
+            raise ValueError("Each element of the ip_adapter_masks array should be a tensor with shape "
+                             "[1, num_images_for_ip_adapter, height, width]. Please use `IPAdapterMaskProcessor` to preprocess your mask")
+        if ip_state.ndim != 4 or mask.shape[1] != ip_state.shape[1]:
+            raise ValueError(f"Number of masks ({mask.shape[1]}) does not match number of ip images "
+                             f"({ip_state.shape[1] if ip_state.ndim == 4 else 'none: a 3-D state'}) at index {index}")
+        if isinstance(scale, list) and not len(scale) == mask.shape[1]:
+            raise ValueError(f"Number of masks ({mask.shape[1]}) does not match number of scales ({len(scale)}) at index {index}")
+    return ip_adapter_masks
+
+
+def _ip_segments(proc, ip_states, ip_adapter_masks, x: torch.Tensor):
+    """The key segments of diffusers' image branches (IPAdapterAttnProcessor2_0, 0.27 - 0.31) for ``ops.processor_fwd(ip_segments=)``:
+    adapter j without a mask is ONE segment of all its ``E T`` tokens with weight ``scale_j``; with a mask ``[1, E, H, W]`` it is E
+    segments, image e with weight ``scale_j[e]`` times the mask's per-row weights.  Adapters and images whose scale is 0 are skipped.
+    float32 storage is refused where a segment would be built (a call whose adapters are all skipped is the text attention alone)."""
+    n, s, _ = x.shape
+    scales = list(proc.scale)
+    if ip_adapter_masks is not None:
+        masks = _check_ip_masks(ip_adapter_masks, scales, ip_states)
+    else:
+        masks = [None] * len(scales)
+    segs = []
+    for ip_state, scale, to_k, to_v, mask in zip(ip_states, scales, proc.to_k_ip, proc.to_v_ip, masks):
+        if isinstance(scale, (list, tuple)):
+            if all(float(v) == 0.0 for v in scale):
+                continue
+        elif float(scale) == 0.0:
+            continue
+        if x.dtype == torch.float32:
+            raise NotImplementedError("several IP-Adapters per layer, ip_adapter_masks and attention_mask beside image embeddings "
+                                      "are implemented for float16 / bfloat16 storage; float32 storage runs one unmasked "
+                                      "adapter per layer")
+        if ip_state.dtype != x.dtype:
+            raise TypeError(f"image embeddings are {ip_state.dtype}, hidden states {x.dtype}")
+        if mask is not None:
+            sc = list(scale) if isinstance(scale, (list, tuple)) else [scale] * mask.shape[1]
+            for e in range(mask.shape[1]):
+                if float(sc[e]) == 0.0:                 # (diffusers adds a zero term there)
+                    continue
+                k, vt = _ip_segment_kv(ip_state, e, n, to_k.weight, to_v.weight)
+                segs.append(dict(k=k, vt=vt, scale=float(sc[e]), row_weight=_ip_row_weight(mask, e, s, x.dtype, x.device)))
+        else:
+            if isinstance(scale, (list, tuple)):        # diffusers multiplies the tensor by the list there
+                raise TypeError("a list scale needs that adapter's ip_adapter_masks entry (one scale per masked image)")
+            if ip_state.ndim not in (3, 4):
+                raise RuntimeError(f"image embeddings must be [R, T, Cc] or [R, E, T, Cc], got {tuple(ip_state.shape)}")
+            k, vt = _ip_segment_kv(ip_state, None, n, to_k.weight, to_v.weight)
+            segs.append(dict(k=k, vt=vt, scale=float(scale), row_weight=None))
+    return segs
 
 
 class HipIPAdapterAttnProcessor(nn.Module):
@@ -621,6 +754,9 @@ class HipIPAdapterAttnProcessor(nn.Module):
     every post-warm-up step of an IP run.  An image-embedding tensor with more rows than frames (the pipelines'
     ``[9, 1, T, Cc]`` for a batch of 3) is folded like diffusers' ``view(batch, -1, heads, head_dim)`` does: frame i
     attends over the tokens of rows ``[i r, (i + 1) r)``.
+    Several adapters per layer, ``ip_adapter_masks`` (regional masks, scalar or per-image list scales) and an ``attention_mask``
+    beside image embeddings run as key segments of one more launch (``_ip_segments``, float16 / bfloat16); the single unmasked
+    adapter keeps the one-call ``ip_*`` form.
     Owns (or shares, see :meth:`wrap`) ``to_k_ip`` / ``to_v_ip`` / ``scale`` / ``num_tokens``."""
 
     def __init__(self, hidden_size: Optional[int] = None, cross_attention_dim: Optional[int] = None,
@@ -648,16 +784,20 @@ class HipIPAdapterAttnProcessor(nn.Module):
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  scale: float = 1.0, ip_adapter_masks=None):
-        if ip_adapter_masks is not None:
-            raise NotImplementedError("ip_adapter_masks are not supported by the HIP path")
         text, ip = _split_ip(encoder_hidden_states, self.num_tokens)
         residual, x, text, shape4, mask = _prologue(attn, hidden_states, text, attention_mask, temb)
         wq, wk, wv, wo, bo = _weights(attn)
         # diffusers' IPAdapterAttnProcessor2_0 masks the TEXT attention only (the image branch runs with attn_mask=None)
         bias = _score_bias(mask, x, x.shape[1] if text is None else text.shape[1], False, "HipIPAdapterAttnProcessor")
-        if bias is not None and ip is not None and float(self.scale[0]) != 0.0:
-            raise NotImplementedError("attention_mask together with image embeddings: the one-call form has no mask for the text "
-                                      "branch alone (AidProcessorArgs.attn_bias is refused with ip)")
+        if ip is not None and (len(ip) != 1 or ip_adapter_masks is not None or bias is not None):
+            # several adapters, regional masks, or a text mask beside image embeddings: the image branches run as key SEGMENTS of one
+            # launch on the call's q / o (aid_processor_ip_fwd); the single unmasked adapter below keeps the ip_* form
+            _no_ip_lora(self)
+            segs = _ip_segments(self, list(ip), ip_adapter_masks, x)
+            y = ops.processor_fwd(x, None if text is None else text.contiguous(), wq, wk, wv, wo, bo, attn.heads,
+                                  mode="plain", attn_bias=bias, ip_segments=segs,
+                                  lora=lora.args(attn, x.dtype, x.device, text is not None))
+            return _epilogue(attn, y, residual, shape4)
         branch = None
         if ip is not None and float(self.scale[0]) != 0.0:
             rows = _ip_token_rows(ip)

@@ -273,6 +273,52 @@ int aid_lerp_kv(const void* k, const void* vt, void* k2, void* vt2, const float*
                 void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * IP-Adapter image attention over several key segments, accumulated into `out` in ONE launch — the image branches of diffusers'
+ * IPAdapterAttnProcessor2_0 with several adapters per layer and / or regional ip_adapter_masks (no ABI version change: two new
+ * entry points, this one and aid_processor_ip_fwd; no existing struct changes).  For every frame i, head h and query row s
+ *     out[i, s, h d : (h + 1) d] = round( float(out[i, s, ...]) + sum_g scale_g * (w_g ? w_g[s] : 1) * softmax(Q K_g^T * softmax_scale) V_g )
+ * over the n_segments <= AID_IP_MAX_SEGMENTS segments: every segment has its own softmax over its own t >= 1 keys, accumulation is
+ * fp32 and the sum is rounded once.  Where aid_attn_fwd(accumulate = 1) adds one segment per launch (a pass over q and out each),
+ * this reads q once, reads out once and writes it once; a zero scale_g or w_g[s] contributes exactly +-0.
+ *   q, out  [n_frames, s, heads*d]   row strides ldq / ldo, frame strides q_fs / o_fs (elements)
+ *   segment: k  [n_rows, t, heads*d] (row stride heads*d, frame stride k_fs), vt [n_rows, heads*d, ldvt] (V TRANSPOSED, frame stride
+ *            vt_fs) — the layouts aid_gemm_nt writes for K = E Wk^T and V^T = Wv E^T; n_rows == n_frames (frame i uses row i) or
+ *            n_rows == 1 (every frame uses row 0; k_fs / vt_fs are then not used); row_weight: device fp32 [s] or NULL.
+ * Reads exactly: q[i, s', h d + c], out[i, s', h d + c] for s' < s, c < d; k[r, j, :heads*d] and vt[r, :heads*d, j] for j < t (rows
+ * >= t of k, columns [t, ldvt) of vt, and everything between the strides never enter the arithmetic: they may hold NaN);
+ * row_weight[0 .. s).  Writes exactly out[i, s', :heads*d].  q and out must not overlap.
+ * Requirements: dtype f16 / bf16 (AID_DTYPE_F32: AID_ERR_DTYPE); d in {40, 64, 80, 160}, ldq / ldo / q_fs / o_fs / k_fs / vt_fs /
+ * ldvt multiples of 8, ldq / ldo >= heads*d, ldvt >= t, q / out / k / vt 16-byte aligned, row_weight 4-byte aligned (AID_ERR_SHAPE);
+ * NULL pointers, n_segments outside 1 .. AID_IP_MAX_SEGMENTS, t < 1, n_rows not 1 / n_frames, softmax_scale <= 0 without
+ * q_prescaled (AID_ERR_ARG).  No allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------- */
+#define AID_IP_MAX_SEGMENTS 8
+
+typedef struct AidIpSegment {
+    const void*  k;
+    const void*  vt;
+    const float* row_weight;     /* device fp32 [s] or NULL (= 1)                             */
+    int64_t k_fs, vt_fs;         /* frame strides in elements                                 */
+    int32_t t, ldvt, n_rows;
+    float   scale;
+} AidIpSegment;
+
+typedef struct AidIpAttnArgs {
+    const void* q;
+    void*       out;
+    const AidIpSegment* segments;   /* HOST array of n_segments entries                       */
+    int32_t n_segments;
+    int32_t n_frames, s, heads, d;
+    int32_t ldq, ldo;
+    int32_t dtype;               /* AID_DTYPE_F16 / AID_DTYPE_BF16                            */
+    int64_t q_fs, o_fs;
+    float   softmax_scale;       /* d^-0.5 for diffusers Attention                            */
+    int32_t q_prescaled;         /* 1: q already holds q * softmax_scale * log2(e)            */
+} AidIpAttnArgs;
+
+int aid_ip_attn_fwd(const AidIpAttnArgs* args /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * One whole processor call (what diffusers' Attention.forward hands to the AID processor):
  *   x   [n_frames, s, c]   hidden states          ctx [n_frames, l, cc] or NULL (self-attn: ctx = x)
  *   wq [c, c]  wk [c, cc]  wv [c, cc]  wo [c, c]  bo [c]      (torch Linear.weight layout [out, in])
@@ -391,6 +437,16 @@ typedef struct AidProcessorArgs {
 
 size_t aid_processor_workspace_bytes(const AidProcessorArgs* args /* host */);
 int    aid_processor_fwd(const AidProcessorArgs* args /* host */, void* stream);
+/* The same call with IMAGE SEGMENTS: n_ip_segs entries of AidIpSegment (a HOST array; more than AID_IP_MAX_SEGMENTS run as several
+ * launches) are added to the attention output by aid_ip_attn_fwd on the call's q / o workspace, after the text attention and before
+ * the out projection — several IP-Adapters per layer, regional masks (AidIpSegment.row_weight); each segment's K / V^T is projected
+ * by the caller (aid_gemm_nt; they do not change over the denoising loop).  AidProcessorArgs itself is unchanged (and so are the ABI
+ * version and aid_processor_workspace_bytes): the segments travel beside it.  n_ip_segs == 0 is aid_processor_fwd.  With segments the
+ * call must be a cross-attention PLAIN call with ip == NULL (AID_ERR_ARG) in a 16-bit dtype (AID_ERR_DTYPE); attn_bias is ALLOWED and
+ * covers the text launch only, as diffusers' IPAdapterAttnProcessor2_0 masks the text scores only.  LoRA / DoRA on the four
+ * projections, k_cached, LayerNorm and residual work as without segments.  Segment errors as aid_ip_attn_fwd; everything is checked
+ * before the first launch. */
+int    aid_processor_ip_fwd(const AidProcessorArgs* args /* host */, const AidIpSegment* ip_segs /* host */, int32_t n_ip_segs, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
