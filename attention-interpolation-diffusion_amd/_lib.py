@@ -21,10 +21,13 @@ MODE_PLAIN, MODE_INNER, MODE_OUTER = 0, 1, 2
 GEMM_MAX_PROBLEMS = 6
 IP_NONE, IP_SAME, IP_PLAIN = 0, 1, 2
 IP_MAX_SEGMENTS = 8
+EP_PUT, EP_GET = 0, 1
+EP_RECORD, EP_REPLAY = 1, 2
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
+    "aid_endpoint_rows", "aid_processor_ep_workspace_bytes", "aid_processor_ep_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -110,6 +113,21 @@ class AidProcessorArgs(C.Structure):
     ]
 
 
+class AidEndpointRows(C.Structure):
+    _fields_ = [
+        ("k", C.c_void_p), ("vt", C.c_void_p), ("k_store", C.c_void_p), ("vt_store", C.c_void_p), ("step", C.c_void_p),
+        ("k_fs", C.c_int64), ("vt_fs", C.c_int64),
+        ("row_begin", C.c_int32), ("row_end", C.c_int32), ("n_steps", C.c_int32), ("direction", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
+class AidEndpointStore(C.Structure):
+    _fields_ = [
+        ("k_store", C.c_void_p), ("vt_store", C.c_void_p), ("step", C.c_void_p),
+        ("n_steps", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
 class AidProfileEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double),
                 ("flops_executed", C.c_double)]
@@ -180,6 +198,12 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.c_void_p]
     lib.aid_processor_ip_fwd.restype = C.c_int
     lib.aid_processor_ip_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.aid_endpoint_rows.restype = C.c_int
+    lib.aid_endpoint_rows.argtypes = [C.POINTER(AidEndpointRows), C.c_void_p]
+    lib.aid_processor_ep_workspace_bytes.restype = C.c_size_t
+    lib.aid_processor_ep_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidEndpointStore)]
+    lib.aid_processor_ep_fwd.restype = C.c_int
+    lib.aid_processor_ep_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidEndpointStore), C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

@@ -142,7 +142,8 @@ struct Carve {
     int rx, rctx;                                         // LoRA: columns of U of x / of ctx
 };
 
-Carve carve(const AidProcessorArgs& a) {
+// kv_extra: rows of k / V^T behind the projected ones (end-point store replay: the begin and the end frame's)
+Carve carve(const AidProcessorArgs& a, int kv_extra = 0) {
     Carve c;
     const size_t es = a.dtype == AID_DTYPE_F32 ? 4 : 2;
     const int nctx = a.ctx ? a.n_ctx : a.n_frames;
@@ -150,8 +151,8 @@ Carve carve(const AidProcessorArgs& a) {
     c.lp = round_up(l, 8);
     size_t off = 0;
     c.q = off;  off += align_up((size_t)a.n_frames * a.s * a.c * es, 256);
-    c.k = off;  off += align_up((size_t)nctx * l * a.c * es, 256);
-    c.vt = off; off += align_up((size_t)nctx * a.c * c.lp * es, 256);
+    c.k = off;  off += align_up((size_t)(nctx + kv_extra) * l * a.c * es, 256);
+    c.vt = off; off += align_up((size_t)(nctx + kv_extra) * a.c * c.lp * es, 256);
     c.o = off;  off += align_up((size_t)a.n_frames * a.s * a.c * es, 256);
     c.k2 = c.vt2 = off;
     if (a.mode == AID_MODE_INNER) {                       // interpolated K / V^T, one row per frame
@@ -612,13 +613,73 @@ size_t aid_processor_workspace_bytes(const AidProcessorArgs* args) {
     return carve(*args).total;
 }
 
-int aid_processor_fwd(const AidProcessorArgs* args, void* stream) { return aid_processor_ip_fwd(args, nullptr, 0, stream); }
+int aid_endpoint_rows(const AidEndpointRows* args, void* stream) {
+    if (!args) return AID_ERR_ARG;
+    const AidEndpointRows& a = *args;
+    if (!a.k || !a.vt || !a.k_store || !a.vt_store || !a.step || !aligned4(a.step)) return AID_ERR_ARG;
+    if (a.row_begin < 0 || a.row_end < 0 || a.n_steps < 1) return AID_ERR_ARG;
+    if (a.direction != AID_EP_PUT && a.direction != AID_EP_GET) return AID_ERR_ARG;
+    if (!dtype_ok(a.dtype)) return AID_ERR_DTYPE;
+    if (a.k_fs < 8 || a.vt_fs < 8 || a.k_fs % 8 || a.vt_fs % 8) return AID_ERR_SHAPE;
+    if (!aligned16(a.k) || !aligned16(a.vt) || !aligned16(a.k_store) || !aligned16(a.vt_store)) return AID_ERR_SHAPE;
+    hipError_t e;
+    {
+        // traffic: the four blocks read once and written once
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_endpoint_rows<%s,%s>", dtype_name(a.dtype), a.direction == AID_EP_PUT ? "put" : "get");
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 0.0, (a.dtype == AID_DTYPE_F32 ? 4.0 : 2.0) * 4.0 * (double)(a.k_fs + a.vt_fs));
+        e = aid::endpoint_rows_launch(a, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_endpoint_rows");
+}
+
+// end-point store beside a processor call (aid_hip.h): self-attention AID calls only
+static int check_endpoint_store(const AidProcessorArgs& a, const AidEndpointStore& ep) {
+    if (ep.mode != AID_EP_RECORD && ep.mode != AID_EP_REPLAY) return AID_ERR_ARG;
+    if (a.ctx || a.mode == AID_MODE_PLAIN || a.ip) return AID_ERR_ARG;
+    if (!ep.k_store || !ep.vt_store || !ep.step || !aligned4(ep.step) || ep.n_steps < 1) return AID_ERR_ARG;
+    if (!aligned16(ep.k_store) || !aligned16(ep.vt_store)) return AID_ERR_SHAPE;
+    return AID_OK;
+}
+
+static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
+                          void* stream);
+
+size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidEndpointStore* ep) {
+    if (!args) return 0;
+    if (!ep) return aid_processor_workspace_bytes(args);
+    AidProcessorArgs a = *args;
+    if (ep->mode == AID_EP_REPLAY) a.begin = a.end = 0;           // not read in replay
+    if (check_processor(a) != AID_OK || check_endpoint_store(a, *ep) != AID_OK) return 0;
+    return carve(a, ep->mode == AID_EP_REPLAY ? 2 : 0).total;
+}
+
+int aid_processor_fwd(const AidProcessorArgs* args, void* stream) { return processor_impl(args, nullptr, 0, nullptr, stream); }
 
 int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, void* stream) {
+    return processor_impl(args, ip_segs, n_ip_segs, nullptr, stream);
+}
+
+int aid_processor_ep_fwd(const AidProcessorArgs* args, const AidEndpointStore* ep, void* stream) {
+    return processor_impl(args, nullptr, 0, ep, stream);
+}
+
+static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
+                          void* stream) {
     if (!args) return AID_ERR_ARG;
-    const AidProcessorArgs& a = *args;
+    AidProcessorArgs a_local;
+    const bool replay = ep && ep->mode == AID_EP_REPLAY;
+    if (replay) {                                         // the end points are rows n_frames / n_frames + 1 of k / V^T (filled from the
+        a_local = *args;                                  // store below); args->begin / args->end are not read
+        a_local.begin = a_local.end = 0;
+    }
+    const AidProcessorArgs& a = replay ? a_local : *args;
     int rc = check_processor(a);
     if (rc != AID_OK) return rc;
+    if (ep) {
+        rc = check_endpoint_store(a, *ep);
+        if (rc != AID_OK) return rc;
+    }
     if (n_ip_segs < 0 || (n_ip_segs == 0 && ip_segs)) return AID_ERR_ARG;
     if (n_ip_segs > 0) {                               // image segments: a cross-attention PLAIN call without the ip_* branch, 16-bit
         if (!a.ctx || a.mode != AID_MODE_PLAIN || a.ip) return AID_ERR_ARG;
@@ -626,7 +687,7 @@ int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_se
         rc = check_ip_segments(ip_segs, n_ip_segs, a.n_frames);
         if (rc != AID_OK) return rc;
     }
-    const Carve cv = carve(a);
+    const Carve cv = carve(a, replay ? 2 : 0);
     if (!a.workspace || a.workspace_bytes < cv.total || !aligned16(a.workspace)) return AID_ERR_WORKSPACE;
     char* ws = static_cast<char*>(a.workspace);
     void* q = ws + cv.q;
@@ -766,6 +827,22 @@ int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_se
     rc = aid_gemm_nt(pr, npr, a.dtype, stream);
     if (rc != AID_OK) return rc;
 
+    // 1b. end-point store: RECORD keeps the end-point rows of this step's k / V^T, REPLAY puts the recorded rows behind the local ones
+    const int kv_rows = replay ? nctx + 2 : nctx;
+    const int begin = replay ? nctx : a.begin, end = replay ? nctx + 1 : a.end;
+    if (ep) {
+        AidEndpointRows er;
+        memset(&er, 0, sizeof(er));
+        er.k = ws + cv.k; er.vt = ws + cv.vt; er.k_store = ep->k_store; er.vt_store = ep->vt_store;
+        er.step = ep->step; er.n_steps = ep->n_steps;
+        er.k_fs = (int64_t)l * a.c; er.vt_fs = (int64_t)a.c * cv.lp;
+        er.row_begin = begin; er.row_end = end;
+        er.direction = replay ? AID_EP_GET : AID_EP_PUT;
+        er.dtype = a.dtype;
+        rc = aid_endpoint_rows(&er, stream);
+        if (rc != AID_OK) return rc;
+    }
+
     // 2. interpolated attention core (INNER: interpolated K / V^T of the interior frames first)
     AidAttnArgs at;
     memset(&at, 0, sizeof(at));
@@ -774,17 +851,17 @@ int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_se
         // begin / end are rows of k / vt (context rows when ctx_map is given); the interpolated rows are per FRAME
         at.k2 = ws + cv.k2; at.vt2 = ws + cv.vt2;
         const int interior = a.n_frames - a.n_plain - 2;
-        rc = lerp_kv_impl(k, vt, ws + cv.k2, ws + cv.vt2, a.coef, a.n_frames, a.begin, a.end, (int64_t)l * a.c,
+        rc = lerp_kv_impl(k, vt, ws + cv.k2, ws + cv.vt2, a.coef, a.n_frames, begin, end, (int64_t)l * a.c,
                           (int64_t)a.c * cv.lp, a.dtype, stream, interior > 0 ? interior : 0);
         if (rc != AID_OK) return rc;
     }
     at.coef = a.coef; at.frame_scale = nullptr; at.kv_map = a.ctx_map;
-    at.n_frames = a.n_frames; at.n_kv = nctx;
+    at.n_frames = a.n_frames; at.n_kv = kv_rows;
     at.s = a.s; at.l = l; at.heads = a.heads; at.d = d;
     at.ldq = a.c; at.ldk = a.c; at.ldvt = cv.lp; at.ldo = a.c;
     at.q_fs = (int64_t)a.s * a.c; at.k_fs = (int64_t)l * a.c; at.vt_fs = (int64_t)a.c * cv.lp; at.o_fs = (int64_t)a.s * a.c;
     at.bias = a.attn_bias; at.bias_fs = a.attn_bias_fs; at.bias_hs = a.attn_bias_hs; at.bias_rs = a.attn_bias_rs;
-    at.mode = a.mode; at.fused = a.fused; at.begin = a.begin; at.end = a.end;
+    at.mode = a.mode; at.fused = a.fused; at.begin = begin; at.end = end;
     at.accumulate = 0; at.dtype = a.dtype;
     at.softmax_scale = 1.0f / sqrtf((float)d);
     at.out_scale = 1.0f;

@@ -43,10 +43,13 @@ def install_sequence_processors(unet, size: int, early: str = "fused_outer", alp
     clear_weight_caches()                    # (see processors.py: in-place weight edits are invisible to the cache keys)
     procs = {}
     for name in unet.attn_processors.keys():
-        p = cls(size=size, is_fused=early.startswith("fused"), alpha=alpha, beta=beta,
+        # (a given schedule may hold ONE coefficient — the interior frame of an end-point-store replay; the Beta schedule it
+        #  replaces needs two points)
+        p = cls(size=size if coef is None else max(size, 2), is_fused=early.startswith("fused"), alpha=alpha, beta=beta,
                 original_attn=HipAttnProcessor())
         if coef is not None:
             assert coef.numel() == size
+            p.size = size
             p.coef = coef.detach().to(torch.float32).cpu().clone()
         procs[name] = p
     unet.set_attn_processor(procs)
@@ -72,6 +75,22 @@ def set_ctx_index(unet, ctx_index: Optional[Sequence[int]]) -> None:
         inner = getattr(proc, "original_attn", None)
         if inner is not None and hasattr(inner, "ctx_index"):
             inner.ctx_index = idx
+
+
+def set_endpoint_store(unet, store, endpoint_ctx: Optional[torch.Tensor] = None, coef=None) -> None:
+    """Attach an ``EndpointStore`` (endpoint_store.py) to every AID processor of ``unet`` for one run — or detach it (``store=None``).
+    Each processor learns its layer's name in the store (its key in ``attn_processors``).  ``endpoint_ctx`` [2, L, Cc]: the text
+    contexts of the two end-point frames, for the cross-attention calls of a REPLAY run; ``coef``: the interior coefficients a replay
+    processor holds (its batch has no end points).  IP-Adapter processors refuse a store at their first call."""
+    for name, proc in unet.attn_processors.items():
+        if isinstance(proc, InterpolatedAttnProcessor):
+            had = getattr(proc, "endpoint_store", None) is not None
+            proc.endpoint_store = store
+            proc.endpoint_layer = name if store is not None else None
+            if store is not None or had:              # (the exchange layout's own endpoint_ctx is left alone)
+                proc.endpoint_ctx = endpoint_ctx
+            if coef is not None:
+                proc.coef = torch.as_tensor(coef, dtype=torch.float32).detach().cpu().clone()
 
 
 def _record_stream(out, stream) -> None:

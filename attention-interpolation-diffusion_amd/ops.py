@@ -16,11 +16,13 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME, MODE_INNER, MODE_OUTER, MODE_PLAIN,
-                   AidAttnArgs, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidProcessorArgs)
+from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME, MODE_INNER, MODE_OUTER, MODE_PLAIN,
+                   AidAttnArgs, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
 IP_MODES = {"same": IP_SAME, "plain": IP_PLAIN}
+EP_MODES = {"record": EP_RECORD, "replay": EP_REPLAY}
+EP_DIRECTIONS = {"put": EP_PUT, "get": EP_GET}
 SUPPORTED_HEAD_DIMS = (40, 64, 80, 160)
 
 
@@ -649,7 +651,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   ip: Optional[dict] = None, ln_folded: Optional[tuple] = None,
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None,
-                  f32_attn_precision: Optional[str] = None, ip_segments: Optional[Sequence[dict]] = None) -> torch.Tensor:
+                  f32_attn_precision: Optional[str] = None, ip_segments: Optional[Sequence[dict]] = None,
+                  ep: Optional[dict] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -674,7 +677,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     the call (AidProcessorArgs.f32_attn_split), None = the package setting at call time (``f32_attn_split_code``).
     ``ip_segments``: image-key segments (``ip_attn_accumulate``'s dicts; ``aid_processor_ip_fwd``) added to the attention output in
     one launch after the text attention — several IP-Adapters per layer, regional masks as ``row_weight``.  A cross-attention
-    ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only."""
+    ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only.
+    ``ep``: the end-point store of the layer, see ``processor_ep_fwd``."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
     attn_split = f32_attn_split_code(f32_attn_precision)
@@ -788,17 +792,105 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     if dt == DTYPE_F32:
         a.f32_split = split
         a.f32_attn_split = attn_split
-    nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
+    est = None
+    if ep is not None:
+        if seg_arr is not None:
+            raise ValueError("an end-point store belongs to a self-attention call: no ip_segments")
+        est = _endpoint_store_args(ep, s, c, x.dtype)
+        nbytes = lib.aid_processor_ep_workspace_bytes(C.byref(a), C.byref(est))
+    else:
+        nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):
         if nbytes == 0:
             # let the library say why
             a.workspace, a.workspace_bytes = None, 0
-            _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
+            if est is not None:
+                _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
+            else:
+                _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
             raise RuntimeError("aid_processor_workspace_bytes returned 0")
         ws = workspace(nbytes, dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        if seg_arr is not None:
+        if est is not None:
+            _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
+        elif seg_arr is not None:
             _lib.check(lib.aid_processor_ip_fwd(C.byref(a), C.addressof(seg_arr), len(seg_arr), _stream()), "aid_processor_ip_fwd")
         else:
             _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
     return out
+
+
+# ---- end-point K / V^T store (aid_hip.h: aid_endpoint_rows, aid_processor_ep_fwd) ---------------------------------------------------
+def endpoint_block_sizes(l: int, c: int) -> Tuple[int, int]:
+    """(k_fs, vt_fs): elements of one end-point block of keys [L, C] and of transposed values [C, round_up(L, 8)]."""
+    return l * c, c * ((l + 7) // 8 * 8)
+
+
+def _check_store_tensors(k_store: torch.Tensor, vt_store: torch.Tensor, step: torch.Tensor, k_fs: int, vt_fs: int,
+                         dtype: torch.dtype) -> int:
+    """Checks a layer's store against the block sizes of a call; returns n_steps."""
+    _require_gpu(k_store, vt_store, step)
+    if k_store.dtype != dtype or vt_store.dtype != dtype:
+        raise TypeError(f"the end-point store holds {k_store.dtype}, the call computes in {dtype}")
+    n_steps = k_store.shape[0]
+    if k_store.ndim != 3 or vt_store.ndim != 3 or tuple(k_store.shape) != (n_steps, 2, k_fs) or tuple(vt_store.shape) != (n_steps, 2, vt_fs) \
+            or not k_store.is_contiguous() or not vt_store.is_contiguous() or n_steps < 1:
+        raise ValueError(f"the end-point store must be k_store [n_steps, 2, {k_fs}] / vt_store [n_steps, 2, {vt_fs}], contiguous; got "
+                         f"{tuple(k_store.shape)} / {tuple(vt_store.shape)}")
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise ValueError("the step index is ONE int32 on the device (rewritten in place between calls)")
+    return n_steps
+
+
+def _endpoint_store_args(ep: dict, l: int, c: int, dtype: torch.dtype) -> AidEndpointStore:
+    k_fs, vt_fs = endpoint_block_sizes(l, c)
+    est = AidEndpointStore()
+    est.n_steps = _check_store_tensors(ep["k_store"], ep["vt_store"], ep["step"], k_fs, vt_fs, dtype)
+    est.k_store, est.vt_store, est.step = ep["k_store"].data_ptr(), ep["vt_store"].data_ptr(), ep["step"].data_ptr()
+    try:
+        est.mode = EP_MODES[ep["mode"]]
+    except (KeyError, TypeError):
+        raise ValueError(f"ep['mode'] must be 'record' or 'replay'; got {ep.get('mode')!r}") from None
+    return est
+
+
+def endpoint_rows(k: torch.Tensor, vt: torch.Tensor, k_store: torch.Tensor, vt_store: torch.Tensor, step: torch.Tensor,
+                  direction: str, row_begin: int = 0, row_end: int = -1) -> None:
+    """Move the blocks ``k[row_begin]``, ``k[row_end]``, ``vt[row_begin]``, ``vt[row_end]`` between a call's k [F, L, C] /
+    vt [F, C, Lp] and slot ``step[0]`` of a layer's store (``k_store`` [n_steps, 2, L C], ``vt_store`` [n_steps, 2, C Lp]) in one
+    launch (``aid_endpoint_rows``): ``direction`` "put" = call -> store, "get" = store -> call.  ``step`` is ONE int32 on the device,
+    read by the kernel; an index outside the store moves nothing."""
+    dev = _require_gpu(k, vt)
+    if k.dtype != vt.dtype or k.ndim != 3 or vt.ndim != 3 or not k.is_contiguous() or not vt.is_contiguous() or k.shape[0] != vt.shape[0]:
+        raise ValueError("k [F, L, C] and vt [F, C, Lp] must be contiguous tensors of one dtype with the same number of rows")
+    f = k.shape[0]
+    a = AidEndpointRows()
+    a.k_fs, a.vt_fs = k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2]
+    a.n_steps = _check_store_tensors(k_store, vt_store, step, a.k_fs, a.vt_fs, k.dtype)
+    a.k, a.vt, a.k_store, a.vt_store, a.step = k.data_ptr(), vt.data_ptr(), k_store.data_ptr(), vt_store.data_ptr(), step.data_ptr()
+    a.row_begin, a.row_end = row_begin % f, row_end % f
+    try:
+        a.direction = EP_DIRECTIONS[direction]
+    except (KeyError, TypeError):
+        raise ValueError(f"direction must be 'put' or 'get'; got {direction!r}") from None
+    a.dtype = _dtype_code(k)
+    with _on(dev):
+        _lib.check(_lib.load().aid_endpoint_rows(C.byref(a), _stream()), "aid_endpoint_rows")
+
+
+def processor_ep_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, wo: torch.Tensor,
+                     bo: Optional[torch.Tensor], heads: int, *, ep: dict, **kwargs) -> torch.Tensor:
+    """A SELF-attention AID processor call with the end-point store of its layer beside it (``aid_processor_ep_fwd``) — still one
+    library call.  ``ep`` = dict(k_store=[n_steps, 2, S C], vt_store=[n_steps, 2, C round_up(S, 8)], step=int32 device [1],
+    mode="record" | "replay"); every other keyword is ``processor_fwd``'s (mode, fused, coef, n_plain, ln, residual, ln_folded,
+    attn_bias, lora, f32_precision, ...).
+    "record": ``processor_fwd`` itself — ``y`` bit for bit — plus the end-point rows ``begin`` / ``end`` of this step's k / V^T put into
+    slot ``step[0]``.  "replay": ``x`` holds the LOCAL frames only (interior coefficients, PLAIN riders); the recorded rows of slot
+    ``step[0]`` are the end points (``begin`` / ``end`` are not read)."""
+    if ep is None:
+        raise ValueError("processor_ep_fwd needs the layer's store (ep=...); without one call processor_fwd")
+    if kwargs.get("ip") is not None or kwargs.get("ip_segments") or kwargs.get("kv_cached") is not None or kwargs.get("ctx_map") is not None:
+        raise ValueError("an end-point store belongs to a self-attention call: no image branch, no cached text keys, no ctx_map")
+    if kwargs.get("mode", "plain") == "plain":
+        raise ValueError("an end-point store belongs to an interpolated (inner / outer) call")
+    return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, ep=ep, **kwargs)

@@ -44,7 +44,8 @@ from . import ops
 from . import processors as P
 from .attn_shim import AttnStackUNet
 from .interp import generate_beta_tensor, linear_interpolation, slerp, spherical_interpolation
-from .loop import EARLY_MODES, install_sequence_processors, set_aid_active, set_ctx_index
+from .endpoint_store import EndpointStore, run_signature
+from .loop import EARLY_MODES, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store
 from .sequence import SequenceBatch, prepare_sequence, prepare_single
 
 
@@ -407,13 +408,18 @@ class InterpolationStableDiffusionPipeline:
                            callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",),
                            # build-specific: embeddings instead of prompt strings / images
                            embeds_start=None, embeds_end=None, embeds_guide=None,
-                           image_embeds_start=None, image_embeds_end=None, use_graphs: Optional[bool] = None, **kwargs):
+                           image_embeds_start=None, image_embeds_end=None, use_graphs: Optional[bool] = None,
+                           endpoints: Optional[EndpointStore] = None, **kwargs):
         """Batch ``[start, target(it), end]`` through the denoising loop (pipeline_interpolated_sd.py:1407-1963).
         ``is_fused`` / ``atype`` are accepted and ignored exactly like the reference (:1418-1419):
         behaviour is set by ``load_aid``.  ``image_embeds_start / _end``: (negative, positive) image-embedding pairs
         ``[1, 1, emb]`` in place of ``image_start`` / ``image_end`` PIL images (whose encoding is diffusers' job).
         ``use_graphs`` (build-specific; None = on a GPU): the three kinds of UNet pass of the loop are captured into
-        hipGraphs at their first step and replayed afterwards (:class:`_PassGraphs`); results are bit-identical to eager."""
+        hipGraphs at their first step and replayed afterwards (:class:`_PassGraphs`); results are bit-identical to eager.
+        ``endpoints`` (build-specific): an :class:`EndpointStore`.  Empty, the run RECORDS the two end points into it (a normal run,
+        bit-identical outputs); recorded under the same end points and settings, the run REPLAYS: only the frame at ``it`` goes
+        through the UNet, its AID steps attend to the stored end-point keys / values, and the end points' outputs come from the
+        stored latents — the return value has the usual three frames.  Anything else raises ``ValueError`` naming what differs."""
         if image_start is not None and image_end is None:
             raise ValueError("Please provide both `image_start` and `image_end` to interpolate, or only `image_end` to "
                              "control the scale.")                                     # pipeline_interpolated_sd.py:1608-1612
@@ -447,10 +453,34 @@ class InterpolationStableDiffusionPipeline:
         cond, unc = batch.cond.to(dev, dtype), batch.uncond.to(dev, dtype)
         graphs = _PassGraphs(_use_graphs(use_graphs, dev))
         P.clear_weight_caches()              # caches derived from weights live for ONE run (in-place weight edits are invisible to their keys)
+        ep_mode, n_run = None, 3
+        if endpoints is not None:
+            if img is not None:
+                raise NotImplementedError("an end-point store with IP-Adapter image inputs: the store holds the text processors' "
+                                          "self-attention keys / values only")
+            early_mode, fusion = self._installed_aid_mode()
+            sig = run_signature(latent_start=latent_start, latent_end=latent_end, embeds_start=cond_s[0], embeds_end=cond_e[0],
+                                embeds_negative=[unc_s[0], unc_e[0]], embeds_pooled=self._pooled_inputs(cond_s, cond_e, unc_s, unc_e),
+                                embeds_guide=[] if guide is None else [g_ for pair in guide for g_ in pair],
+                                num_inference_steps=num_inference_steps, warmup_ratio=warmup_ratio, early=early_mode, late="self",
+                                fusion=fusion, guidance_scale=gs, dtype=dtype, timesteps=self.scheduler.timesteps, unet=self.unet,
+                                lora_scale=ls)
+            if endpoints.recorded:
+                endpoints.begin_replay(sig, dev)
+                ep_mode, n_run = "replay", 1
+                ectx = torch.cat([cond[0:1], cond[2:3]]).contiguous()
+                lat, cond, unc = lat[1:2], cond[1:2].contiguous(), unc[1:2].contiguous()
+                if pooled is not None:
+                    pooled = (pooled[0][1:2], pooled[1][1:2])
+                set_endpoint_store(self.unet, endpoints, endpoint_ctx=ectx, coef=[it])
+            else:
+                endpoints.begin_record(sig, warmup_steps, dev)
+                ep_mode = "record"
+                set_endpoint_store(self.unet, endpoints)
 
         # loop-invariant conditioning, moved to the device once (the reference rebuilds the dict every step, :1850-1867)
-        added_c = self._added_cond(None if pooled is None else pooled[0], 3, None if img is None else img[0])
-        added_u = self._added_cond(None if pooled is None else pooled[1], 3, None if img is None else img[1])
+        added_c = self._added_cond(None if pooled is None else pooled[0], n_run, None if img is None else img[0])
+        added_u = self._added_cond(None if pooled is None else pooled[1], n_run, None if img is None else img[1])
 
         def cond_pass(x, t):
             return self._unet(x, t, cond, added_c, cak)
@@ -458,21 +488,36 @@ class InterpolationStableDiffusionPipeline:
         def uncond_pass(x, t):
             return self._unet(x, t, unc, added_u, cak)
 
-        for i, t in enumerate(self.scheduler.timesteps):
-            x = self.scheduler.scale_model_input(lat, t)
-            td = _dev_scalar(t, dev) if graphs.enabled else t
-            if i < warmup_steps:                                                       # :1845-1848
-                self.activate_aid(it)
-            else:
-                self.deactivate_aid()
-            noise_text = graphs.run(("cond", i < warmup_steps), cond_pass, x=x, t=td)
-            self.deactivate_aid()                                                      # :1870
-            noise_unc = graphs.run(("uncond",), uncond_pass, x=x, t=td)
-            noise = noise_unc + gs * (noise_text - noise_unc)                          # :1892
-            lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
-            if callback_on_step_end is not None:
-                out = callback_on_step_end(self, i, t, {"latents": lat}) or {}
-                lat = out.pop("latents", lat)
+        try:
+            for i, t in enumerate(self.scheduler.timesteps):
+                x = self.scheduler.scale_model_input(lat, t)
+                td = _dev_scalar(t, dev) if graphs.enabled else t
+                if i < warmup_steps:                                                       # :1845-1848
+                    if ep_mode == "replay":
+                        set_aid_active(self.unet, True)        # the processors hold the interior coefficient alone (set above)
+                    else:
+                        self.activate_aid(it)
+                    if ep_mode is not None:
+                        endpoints.set_step(i)
+                else:
+                    self.deactivate_aid()
+                key = ("cond", i < warmup_steps) if ep_mode is None else ("cond", i < warmup_steps, ep_mode)
+                noise_text = graphs.run(key, cond_pass, x=x, t=td)
+                self.deactivate_aid()                                                      # :1870
+                noise_unc = graphs.run(("uncond",), uncond_pass, x=x, t=td)
+                noise = noise_unc + gs * (noise_text - noise_unc)                          # :1892
+                lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
+                if callback_on_step_end is not None:
+                    out = callback_on_step_end(self, i, t, {"latents": lat}) or {}
+                    lat = out.pop("latents", lat)
+            if ep_mode == "record":
+                endpoints.finish_record(torch.cat([lat[0:1], lat[2:3]]))
+            elif ep_mode == "replay":
+                lat = torch.cat([endpoints.latents[0:1], lat, endpoints.latents[1:2]], dim=0)
+        finally:
+            if ep_mode is not None:
+                endpoints.abort()                # (no-op after finish_record; a failed recording leaves nothing behind)
+                set_endpoint_store(self.unet, None)
         image = self._decode(lat, "latent" if output_type == "latent" else ("np" if output_type in ("pil", "np") else output_type))
         return {"images": image} if return_dict else (image, None)
 
@@ -486,14 +531,15 @@ class InterpolationStableDiffusionPipeline:
                     # build-specific
                     embeds_start=None, embeds_end=None, embeds_guide=None, batched_cfg: bool = True,
                     output_type: str = "np", coef: Optional[Sequence[float]] = None, use_graphs: Optional[bool] = None,
-                    cross_attention_kwargs: Optional[Dict[str, Any]] = None):
+                    cross_attention_kwargs: Optional[Dict[str, Any]] = None, endpoints: Optional[EndpointStore] = None):
         """gradio_src/pipeline_interpolated_stable_diffusion.py:163-304 with the root pipelines' warm-up count
         (``i < int(T * warmup_ratio)`` with 0-based ``i``).  ``late`` must be "self" (plain
         attention) or one of the AID modes.  ``batched_cfg``: the two passes of a step run as one UNet call.
         ``coef`` (build-specific, ``[0, t_1, ..., 1]``): render the frames at THESE coefficients the way
         ``interpolate_single(t_k)`` would — latents slerp'd and embeddings lerp'd at ``t_k``, attention coefficient
         ``t_k`` — in one N-frame run (the Beta-prior exploration fills several gaps per run with it, prior.py).
-        ``use_graphs`` and ``cross_attention_kwargs`` as in ``interpolate_single``.  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
+        ``use_graphs``, ``cross_attention_kwargs`` and ``endpoints`` as in ``interpolate_single`` (a replay renders the ``size - 2``
+        interior frames; a store recorded by either method replays in the other).  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
         back when the run ends (the run works with its own N-frame processors)."""
         if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
             raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
@@ -526,15 +572,45 @@ class InterpolationStableDiffusionPipeline:
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         warmup_steps = int(num_inference_steps * warmup_ratio)
         installed = dict(self.unet.attn_processors)          # what load_aid / load_aid_ip_adapter put there: restored at the end
+        ep_mode, full_size = None, size
+        if endpoints is not None:
+            if size < 3:
+                raise ValueError("an end-point store needs at least one interior frame (size >= 3)")
+            sig = run_signature(latent_start=latent_start.to(dev, dtype), latent_end=latent_end.to(dev, dtype), embeds_start=cond_s[0],
+                                embeds_end=cond_e[0], embeds_negative=[unc_s[0], unc_e[0]],
+                                embeds_pooled=self._pooled_inputs(cond_s, cond_e, unc_s, unc_e),
+                                embeds_guide=[] if guide is None else [g_ for pair in guide for g_ in pair],
+                                num_inference_steps=num_inference_steps, warmup_ratio=warmup_ratio,
+                                early=early.split("_")[1], late=late, fusion=early.startswith("fused"), guidance_scale=gs, dtype=dtype,
+                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls)
+            if endpoints.recorded:
+                endpoints.begin_replay(sig, dev)
+                ep_mode = "replay"
+            else:
+                endpoints.begin_record(sig, warmup_steps if late == "self" else num_inference_steps, dev)
+                ep_mode = "record"
         try:
-            procs = {}
-            for mode in {early} | ({late} - {"self"}):
-                install_sequence_processors(self.unet, size, early=mode, alpha=alpha, beta=beta,
-                                            num_inference_steps=num_inference_steps, coef=batch.coef)
-                procs[mode] = dict(self.unet.attn_processors)
             cond, unc = batch.cond.to(dev, dtype), batch.uncond.to(dev, dtype)
             idx = [int(i) for i in batch.ctx_index.tolist()] if batch.n_distinct_ctx != size else None
             lat = batch.latents
+            n_distinct = batch.n_distinct_ctx
+            run_coef, ectx = batch.coef, None
+            if ep_mode == "replay":          # the batch holds the interior frames only; the end points' text contexts ride behind theirs
+                ectx = torch.cat([cond[0:1], cond[-1:]]).contiguous()
+                lat, cond, unc = lat[1:-1], cond[1:-1].contiguous(), unc[1:-1].contiguous()
+                run_coef = batch.coef[1:-1]
+                if pooled is not None:
+                    pooled = (pooled[0][1:-1], pooled[1][1:-1])
+                if idx is not None:          # guide prompt: the interior frames share ONE context
+                    idx, n_distinct = [j - 1 for j in idx[1:-1]], n_distinct - 2
+                size = size - 2
+            procs = {}
+            for mode in {early} | ({late} - {"self"}):
+                install_sequence_processors(self.unet, size, early=mode, alpha=alpha, beta=beta,
+                                            num_inference_steps=num_inference_steps, coef=run_coef)
+                if ep_mode is not None:
+                    set_endpoint_store(self.unet, endpoints, endpoint_ctx=ectx)
+                procs[mode] = dict(self.unet.attn_processors)
             graphs = _PassGraphs(_use_graphs(use_graphs, dev))
             ctx_both = torch.cat([cond, unc]) if batched_cfg else None      # ONE tensor for the whole run: the text K / V cache keys on it
             if batched_cfg:
@@ -557,25 +633,45 @@ class InterpolationStableDiffusionPipeline:
                 td = _dev_scalar(t, dev) if graphs.enabled else t
                 mode = early if i < warmup_steps else late
                 self.unet.set_attn_processor(procs[mode] if mode != "self" else procs[early])
+                if ep_mode is not None and mode != "self":
+                    endpoints.set_step(i)
+                gkey = (mode,) if ep_mode is None else (mode, ep_mode)
                 if batched_cfg:
                     set_aid_active(self.unet, mode != "self", plain_tail=size if mode != "self" else 0)
-                    set_ctx_index(self.unet, None if idx is None else idx + [j + batch.n_distinct_ctx for j in idx])
-                    both = graphs.run(("both", mode), both_pass, x=x, t=td)
+                    set_ctx_index(self.unet, None if idx is None else idx + [j + n_distinct for j in idx])
+                    both = graphs.run(("both",) + gkey, both_pass, x=x, t=td)
                     noise_text, noise_unc = both[:size], both[size:]
                 else:
                     set_ctx_index(self.unet, idx)
                     set_aid_active(self.unet, mode != "self")
-                    noise_text = graphs.run(("cond", mode), cond_pass, x=x, t=td)
+                    noise_text = graphs.run(("cond",) + gkey, cond_pass, x=x, t=td)
                     set_aid_active(self.unet, False)
-                    noise_unc = graphs.run(("uncond", mode), uncond_pass, x=x, t=td)
+                    noise_unc = graphs.run(("uncond",) + gkey, uncond_pass, x=x, t=td)
                 noise = noise_unc + gs * (noise_text - noise_unc)
                 lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
+            if ep_mode == "record":
+                endpoints.finish_record(torch.cat([lat[0:1], lat[-1:]]))
+            elif ep_mode == "replay":
+                lat = torch.cat([endpoints.latents[0:1], lat, endpoints.latents[1:2]], dim=0)
         finally:
+            if ep_mode is not None:
+                endpoints.abort()                # (no-op after finish_record; a failed recording leaves nothing behind)
             set_ctx_index(self.unet, None)
             self.unet.set_attn_processor(installed)
         return self._decode(lat, output_type)
 
     # -- small shape helpers (overridden by the XL class) ----------------------------------------------
+    def _installed_aid_mode(self):
+        """("outer" | "inner", is_fused) of the AID processors ``load_aid`` installed — what ``interpolate_single`` renders with."""
+        for proc in self.unet.attn_processors.values():
+            if isinstance(proc, P.InterpolatedAttnProcessor) and proc._mode is not None:
+                return proc._mode, bool(proc.is_fused)
+        raise RuntimeError("no AID processors installed: call load_aid first")
+
+    def _pooled_inputs(self, cond_s, cond_e, unc_s, unc_e):
+        """The pooled embeddings a run's signature covers (SDXL), [] for SD."""
+        return [e[1] for e in (cond_s, cond_e, unc_s, unc_e) if len(e) > 1]
+
     def _split(self, embs):
         """(cond, uncond) -> ((cond,), (uncond,)); the XL class carries pooled embeddings in slot 1."""
         return (embs[0],), (embs[1],)

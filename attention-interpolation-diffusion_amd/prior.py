@@ -243,14 +243,19 @@ class BetaPriorPipeline:
     are on (the reference moves every frame through CPU PIL preprocessing).
     Rendering: ``pipe.interpolate_single(t, ...)`` per new point like the reference, or — ``batch`` > 1 — one N-frame
     ``pipe.interpolate`` run over ``[0, *ts, 1]`` filling several gaps at once (the processors take any coefficient vector).
+    ``reuse_endpoints`` (build-specific): every render of an exploration runs between the same two end points, so the first one
+    records them into an ``EndpointStore`` and the later ones replay it — only the new frames go through the UNet.
     """
 
-    def __init__(self, pipe, model_ID: str = "openai/clip-vit-base-patch32", model=None, preprocess=None):
+    def __init__(self, pipe, model_ID: str = "openai/clip-vit-base-patch32", model=None, preprocess=None,
+                 reuse_endpoints: bool = False):
         if model is None:
             from transformers import CLIPImageProcessor, CLIPModel      # needs the checkpoint on disk (no network here)
             model = CLIPModel.from_pretrained(model_ID)
             preprocess = preprocess or CLIPImageProcessor.from_pretrained(model_ID)
         self.model, self.preprocess, self.pipe = model, preprocess, pipe
+        self.reuse_endpoints = bool(reuse_endpoints)
+        self.endpoints = None                          # the store of the exploration in progress (reuse_endpoints)
 
     def _compute_clip(self, embedding_a, embedding_b):
         return clip_distance(embedding_a, embedding_b)
@@ -282,6 +287,8 @@ class BetaPriorPipeline:
     def _render(self, ts, prompt_start, prompt_end, negative_prompt, latent_start, latent_end, num_inference_steps, kw):
         """Frames at ``[0, *ts, 1]``: batch-3 ``interpolate_single`` for one point (the reference's call, prior.py:94-104),
         an N-frame ``interpolate`` with the coefficient vector for several."""
+        if self.endpoints is not None:
+            kw = dict(kw, endpoints=self.endpoints)
         if len(ts) == 1:
             out = self.pipe.interpolate_single(ts[0], prompt_start=prompt_start, prompt_end=prompt_end,
                                                negative_prompt=negative_prompt, latent_start=latent_start,
@@ -302,6 +309,9 @@ class BetaPriorPipeline:
                           num_inference_steps=28, exploration_size=16, init_alpha=3, init_beta=3, uniform=False,
                           batch: int = 1, **kwargs):
         kwargs.pop("early", None)                      # accepted and ignored like the reference
+        if self.reuse_endpoints:                       # one store per exploration: its first render records, the others replay
+            from .endpoint_store import EndpointStore
+            self.endpoints = EndpointStore()
         ex = BetaPriorExplorer(lambda ts: self._render(ts, prompt_start, prompt_end, negative_prompt, latent_start,
                                                        latent_end, num_inference_steps, kwargs), self._compute_clip)
         return ex.explore(exploration_size, init_alpha, init_beta, uniform=uniform, batch=batch)

@@ -70,6 +70,12 @@ class InterpolatedAttnProcessor(nn.Module):
         # ([2, L, Cc]: text contexts of frames 0 and N-1, known to every rank) serves the cross-attention calls.
         self.endpoint_exchange = None
         self.endpoint_ctx: Optional[torch.Tensor] = None
+        # build-specific: the time-domain twin of the exchange.  ``endpoint_store`` (endpoint_store.EndpointStore, set
+        # per run by ``loop.set_endpoint_store``) RECORDS the end points' self-attention keys / values of every AID step, or — in a
+        # run whose batch holds only further interior frames, ``coef`` their coefficients — REPLAYS them; ``endpoint_layer`` names
+        # this processor's layer in the store, ``endpoint_ctx`` serves the cross-attention calls of a replay as above.
+        self.endpoint_store = None
+        self.endpoint_layer: Optional[str] = None
 
     # ``coef`` stays a plain CPU tensor attribute like the reference's (interpolation.py:21-27, 42); assigning it
     # (``activate(t)``, ``proc.coef = ...``) refreshes the device copies at once, so a replayed graph never sees the
@@ -422,12 +428,31 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
     ctx_map = idx = None
     ctx_index = proc.ctx_index if ctx_index is None else ctx_index
     exchange = getattr(proc, "endpoint_exchange", None)
-    if exchange is not None and mode != "plain":
-        if lora.any_lora(attn) and any(lora.active(m) for m in lora.projections(attn)):
+    store = getattr(proc, "endpoint_store", None) if mode != "plain" else None
+    replay = store is not None and store.mode == "replay"
+    if store is not None:
+        if exchange is not None:
+            raise NotImplementedError("an end-point store together with endpoint_exchange: the store replays recorded end points in "
+                                      "a single-device batch, the exchange fetches live ones from their owner ranks — use one")
+        if not x.is_cuda:
+            raise NotImplementedError("an end-point store on a CPU tensor: the store lives in device memory and is read by the HIP "
+                                      "kernels (there is no CPU path)")
+        if ctx is None:                               # self-attention: one library call with the layer's store beside it
+            fused = proc.is_fused
+            ep = store.ep_args(proc.endpoint_layer or f"layer@{id(attn):x}", x.shape[1], x.shape[2], x.dtype, x.device)
+            y = ops.processor_ep_fwd(x, wq, wk, wv, wo, bo, attn.heads, ep=ep, mode=mode, fused=fused, coef=coef,
+                                     begin=begin, end=0 if replay else end, n_plain=proc.plain_tail, ln=ln, residual=add_to,
+                                     ln_folded=ln_folded,
+                                     seg_executed=ops.executed_segments(mode, fused, vals, x.shape[0], None, begin, end),
+                                     attn_bias=bias, lora=lora.args(attn, x.dtype, x.device, False))
+            return _epilogue(attn, y, residual, shape4)
+    if (exchange is not None or replay) and mode != "plain":
+        # (a store's replay is one processor_fwd call below: LoRA, masks and the fused sublayer ride along)
+        if not replay and lora.any_lora(attn) and any(lora.active(m) for m in lora.projections(attn)):
             raise NotImplementedError("unmerged LoRA adapters in the end-point exchange layout: fuse them (fuse_lora()) first")
-        if bias is not None:
+        if bias is not None and not replay:
             raise NotImplementedError("the end-point exchange layout takes no attention_mask")
-        if ln is not None or add_to is not None:
+        if (ln is not None or add_to is not None) and not replay:
             raise NotImplementedError("the end-point exchange layout runs the plain processor call (no sublayer fusion)")
         n = x.shape[0]
         if ctx is None:                               # self-attention: keys / values of frames 0 / N-1 come from their owners
@@ -440,8 +465,8 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
                              begin=begin, end=end, n_plain=proc.plain_tail)
             return _epilogue(attn, ops.linear(o, wo, bo), residual, shape4)
         if proc.endpoint_ctx is None:
-            raise RuntimeError("endpoint_exchange is set: cross-attention needs `endpoint_ctx` (text contexts of the two "
-                               "end-point frames)")
+            raise RuntimeError("endpoint_exchange / a replaying endpoint_store is set: cross-attention needs `endpoint_ctx` (text "
+                               "contexts of the two end-point frames)")
         # local frames keep their (possibly shared) context rows; the two end-point contexts are appended behind them
         base = [int(i) for i in ctx_index] if ctx_index is not None else list(range(n))
         nctx = max(base) + 1
@@ -475,9 +500,11 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
         full = hit[0]
         full_map = base + [nctx, nctx + 1]
         ctx2, ctx_map, idx2 = _shared_context(proc._ctx_cache, full_map, full, n + 2)
+        kv = _text_kv(attn, full, ctx2, idx2, wk, wv)
         y = ops.processor_fwd(x, ctx2, wq, wk, wv, wo, bo, attn.heads, mode=mode, fused=proc.is_fused, coef=coef,
-                              begin=nctx, end=nctx + 1, ctx_map=ctx_map[:n], n_plain=proc.plain_tail,
-                              kv_cached=_text_kv(attn, full, ctx2, idx2, wk, wv))
+                              begin=nctx, end=nctx + 1, ctx_map=ctx_map[:n], n_plain=proc.plain_tail, kv_cached=kv,
+                              ln=ln, residual=add_to, ln_folded=ln_folded, attn_bias=bias,
+                              lora=lora.args(attn, x.dtype, x.device, True, kv=kv is None) if replay else None)
         return _epilogue(attn, y, residual, shape4)
     if ctx is not None and ctx_index is not None:
         ctx, ctx_map, idx = _shared_context(proc._ctx_cache, ctx_index, ctx, x.shape[0])
@@ -867,6 +894,9 @@ class _IPBase(InterpolatedAttnProcessor):
             raise RuntimeError(f"The expanded size of the tensor must match the existing size ({mask.shape[-1]}) at non-singleton "
                                "dimension 2: the IP processors apply the text attention_mask to the image-token scores as well "
                                "(interpolation.py:141-143, 352-359) — the reference fails at that broadcast; pass no mask")
+        if getattr(self, "endpoint_store", None) is not None:
+            raise NotImplementedError("an end-point store on an IP-Adapter processor: the image branch attends to the end points' image "
+                                      "keys, which the store does not hold (text processors only)")
         n = self._frames(x)
         wq, wk, wv, wo, bo = _weights(attn)
         coef, vals = self._coef_state(x.device, x.dtype, x.shape[0])

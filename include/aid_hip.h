@@ -449,6 +449,71 @@ int    aid_processor_fwd(const AidProcessorArgs* args /* host */, void* stream);
 int    aid_processor_ip_fwd(const AidProcessorArgs* args /* host */, const AidIpSegment* ip_segs /* host */, int32_t n_ip_segs, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * End-point K / V^T store (no ABI version change: three new entry points, no existing struct changes).  The two end-point frames of
+ * an AID run need nothing from the interior frames (with coefficient 0 / 1 every mode is plain attention of that frame), so their
+ * self-attention keys / values per (layer, AID step) can be RECORDED in one run and further interior frames rendered against them in
+ * later runs whose batch holds the new frames only (REPLAY).  A store of one layer:
+ *   k_store  [n_steps, 2, k_fs]    vt_store [n_steps, 2, vt_fs]      (entry 0 = begin frame, 1 = end frame; element type of the call)
+ * aid_endpoint_rows moves, in ONE streaming launch, the four contiguous blocks k[row_begin], k[row_end] (k_fs elements each) and
+ * vt[row_begin], vt[row_end] (vt_fs elements each; rows are k_fs / vt_fs apart) between a call's k / vt tensors and slot *step:
+ *   AID_EP_PUT  reads  k[row_begin * k_fs .. + k_fs), k[row_end * k_fs .. + k_fs), vt[row_begin * vt_fs .. + vt_fs),
+ *                      vt[row_end * vt_fs .. + vt_fs) and *step;
+ *               writes k_store[(2 * *step + e) * k_fs .. + k_fs), vt_store[(2 * *step + e) * vt_fs .. + vt_fs) for e = 0, 1
+ *   AID_EP_GET  reads what PUT writes (and *step), writes what PUT reads.  Nothing else is read or written.
+ * The whole block moves — gap rows and V^T pad columns included, as aid_lerp_kv lerps them.  `step` is a DEVICE pointer read by the
+ * kernel, like the coefficient buffers: a launch captured into a graph addresses another slot at every replay with no node update.
+ * A *step outside [0, n_steps) moves nothing (a memory-safety guard, not a mode: the host keeps the index in range).
+ * Requirements as aid_lerp_kv: k_fs / vt_fs positive multiples of 8, k / vt / k_store / vt_store 16-byte aligned (AID_ERR_SHAPE);
+ * f16 / bf16 / f32 (AID_ERR_DTYPE); NULL pointers, step not 4-byte aligned, negative rows, n_steps < 1, a direction other than
+ * PUT / GET (AID_ERR_ARG) — all before any launch.  16-byte vector loads and stores on a grid-stride walk; no atomics, no LDS.
+ * ------------------------------------------------------------------------------------- */
+#define AID_EP_PUT 0          /* call  -> store */
+#define AID_EP_GET 1          /* store -> call  */
+
+typedef struct AidEndpointRows {
+    void*          k;            /* [rows, k_fs]  of the call                                  */
+    void*          vt;           /* [rows, vt_fs] of the call                                  */
+    void*          k_store;      /* [n_steps, 2, k_fs]                                         */
+    void*          vt_store;     /* [n_steps, 2, vt_fs]                                        */
+    const int32_t* step;         /* DEVICE: the slot index, read by the kernel                 */
+    int64_t k_fs, vt_fs;         /* block sizes = row strides, in elements                     */
+    int32_t row_begin, row_end;  /* rows of k / vt                                             */
+    int32_t n_steps;
+    int32_t direction;           /* AID_EP_PUT / AID_EP_GET                                    */
+    int32_t dtype;               /* AID_DTYPE_*                                                */
+} AidEndpointRows;
+
+int aid_endpoint_rows(const AidEndpointRows* args /* host */, void* stream);
+
+/* aid_processor_fwd with the store of its layer beside it (AidProcessorArgs is unchanged).  ep == NULL is aid_processor_fwd.
+ *   AID_EP_RECORD  exactly aid_processor_fwd(args) plus one AID_EP_PUT of rows args->begin / args->end of the call's k / V^T behind
+ *                  the projection launch: y is bit-identical, aid_processor_ep_workspace_bytes == aid_processor_workspace_bytes.
+ *   AID_EP_REPLAY  `args` describes the LOCAL frames only — interior frames (0 < coef < 1) and PLAIN riders (negative coef).  The
+ *                  workspace gives k / V^T two rows more than n_frames: the projections fill rows 0 .. n_frames - 1, one AID_EP_GET
+ *                  fills rows n_frames (begin) and n_frames + 1 (end), and the rest of the call — the lerp of INNER, every attention
+ *                  kernel, the out projection, the epilogues — runs unchanged with begin = n_frames, end = n_frames + 1.
+ *                  args->begin / args->end are not read.
+ * The store's blocks are k_fs = s * c and vt_fs = c * round_up(s, 8) elements of args->dtype.  Both modes are self-attention AID
+ * calls: ctx != NULL, mode == AID_MODE_PLAIN, ip != NULL, a NULL store pointer, n_steps < 1 or a mode other than RECORD / REPLAY is
+ * AID_ERR_ARG, a misaligned store AID_ERR_SHAPE — checked, with everything aid_processor_fwd checks, before the first launch.
+ * LoRA / DoRA, attn_bias, LayerNorm (folded or not), residual, f32_split / f32_attn_split work as in aid_processor_fwd: it is the
+ * same code path.  Cross-attention needs no store: the end points' text contexts are loop-invariant, a replay call appends them to
+ * ctx and points ctx_map / begin / end of aid_processor_fwd at them. */
+#define AID_EP_RECORD 1
+#define AID_EP_REPLAY 2
+
+typedef struct AidEndpointStore {
+    void*          k_store;      /* [n_steps, 2, s * c]                                        */
+    void*          vt_store;     /* [n_steps, 2, c * round_up(s, 8)]                           */
+    const int32_t* step;         /* DEVICE: the AID step of this call                          */
+    int32_t n_steps;
+    int32_t mode;                /* AID_EP_RECORD / AID_EP_REPLAY                              */
+} AidEndpointStore;
+
+size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args /* host */, const AidEndpointStore* ep /* host */);
+int    aid_processor_ep_fwd(const AidProcessorArgs* args /* host */, const AidEndpointStore* ep /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
