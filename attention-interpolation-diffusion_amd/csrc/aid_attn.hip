@@ -84,6 +84,7 @@ struct OState {
     f32x16 o[QB][NDB];
     f32x16 ol[QB];                      // only used when XL
     f32x16 cn[QB];                      // -m in all 16 registers (C operand of the first MFMA), kept when PERSIST_C
+    float  bref;                        // BIAS: largest (clamped) bias value of the row so far; m is relative to it (see tile())
 };
 
 typedef __amdgpu_buffer_rsrc_t Rsrc;
@@ -409,14 +410,51 @@ __global__ __launch_bounds__(NW * 64) void aid_attn_kernel(const AttnKParams p) 
                 }
             }
             };
-            if (LAZY0 && st.mz) qk(std::true_type{});
-            else                qk(std::false_type{});
+            float bshift = 0.f;                                 // BIAS: what raising the bias reference takes off the row reference m
+            if (BIAS) {
+                // the tile's largest (clamped) bias value per row -> st.bref, before the scores take their registers (see below)
+                float bm = -1e30f;
+                int last = L - 1;
+                asm volatile("" : "+s"(last));                  // opaque: the 32 clamped addresses of a ragged tile are formed again in
+                                                                // the score pass, not kept in 64 registers across the products
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {               // eight loads in flight at a time
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const int key = min(key0 + 32 * b + 16 * u + 8 * hi + e, last);
+                            bm = fmaxf(bm, (float)brow[key]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                asm volatile("" ::: "memory");                  // (the score pass loads again: 32 values are not kept live)
+                bm = max_halves(bm);                            // the row's 64 keys sit in two lanes
+                const float bnew = st.fresh ? bm : fmaxf(st.bref, bm);
+                bshift = st.fresh ? 0.f : (st.bref - bnew) * 1.4426950408889634f;      // <= 0
+                st.bref = bnew;
+            }
+            if (BIAS || (LAZY0 && st.mz)) qk(std::true_type{});   // BIAS: plain products, the reference is subtracted below
+            else                          qk(std::false_type{});
             // lane (q, hi): sc[j][b][r] belongs to key  key0 + 32 b + 16 (r>>3) + 8 hi + (r&7)
             if (BIAS) {
                 // scores = scale q k^T + bias (baddbmm(attention_mask, q, k^T, beta = 1, alpha = scale)); the kernel works in the log2
-                // domain.  Values below -1e30 (-inf, finfo.min of bf16) are clamped there: the key then weighs exp(-1e30) = 0 like in
-                // the reference, and a row whose keys are ALL masked averages them uniformly (the reference: uniform for finfo.min, NaN
-                // for -inf).  2-byte loads: a mask row (L elements, any L) has no alignment to offer; correctness-first path.
+                // domain.  Values below -1e30 (-inf, finfo.min of bf16) are clamped there.
+                // The row reference is kept in two parts, st.bref (the largest bias value of the row so far) + st.m, and the exponent
+                // argument of a key is formed as  (q k - m) + (bias - bref) log2(e): the products start from a ZERO accumulator and
+                // both differences are taken in registers, so a mask value of any size costs the live scores no bits (q k - 1.44e30
+                // in one fp32 would be -1.44e30 for every key), and neither reference is ever the argument of an exponential.
+                //  * a masked key next to a live one (in its tile or in another) gets 2^-14427 (-10000), 2^-94503 (fp16 finfo.min) or
+                //    2^-1.44e30 (-inf, bf16 finfo.min): exactly 0 in fp32, like in the reference;
+                //  * a tile whose keys are all masked is averaged by its q k alone (bias - bref = 0 for each of its keys) until a live
+                //    key arrives in a later tile: bref rises by the mask value, m falls by it, and alpha = 2^(m_old - m_new) below takes
+                //    everything accumulated so far to exactly 0.  After a live tile such a tile adds exact zeros;
+                //  * a row whose keys are ALL masked with one value is therefore softmax(scale q k^T) V over all its keys for each of
+                //    the three values — what the reference computes for -10000 and for finfo.min (it adds one constant to the row;
+                //    in fp16 / bf16 its sum rounds to that constant and its answer degrades to uniform weights); for -inf the
+                //    reference's answer is NaN and this is the finite stand-in.
+                // 2-byte loads, each row read twice (maximum, then scores): a mask row (L elements, any L) has no alignment to offer
+                // and d = 160 no registers to hold 32 values; correctness-first path.
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -424,7 +462,9 @@ __global__ __launch_bounds__(NW * 64) void aid_attn_kernel(const AttnKParams p) 
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const int key = min(key0 + 32 * b + 16 * u + 8 * hi + e, L - 1);
-                            sc[0][b][8 * u + e] += fmaxf((float)brow[key], -1e30f) * 1.4426950408889634f;
+                            float db = fmaxf((float)brow[key], -1e30f) - st.bref;
+                            asm volatile("" : "+v"(db));        // the difference first: -ffast-math may not spread it over the sum
+                            sc[0][b][8 * u + e] += db * 1.4426950408889634f;
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -450,8 +490,34 @@ __global__ __launch_bounds__(NW * 64) void aid_attn_kernel(const AttnKParams p) 
             float xall = xm[0];
 #pragma unroll
             for (int j = 1; j < QB; ++j) xall = fmaxf(xall, xm[j]);
-            bool need = __any(xall > XTH);
-            if (st.fresh) {
+            if (BIAS) {
+                // classic online softmax, every tile and per row: the reference follows the row maximum, so P <= 1.  The first tile
+                // of a row sets it and rescales nothing (O and l are zero); bshift re-expresses the old reference relative to the
+                // bias reference this tile may have raised — after a fully masked tile that is -1.44e30 and alpha is exactly 0.
+                const float rowmax = max_halves(xm[0]);
+                const float mold = st.m[0] + bshift;
+                const float mnew = st.fresh ? rowmax : fmaxf(mold, rowmax);
+                if (!st.fresh) {
+                    const float alpha = __builtin_amdgcn_exp2f(mold - mnew);
+#pragma unroll
+                    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) st.o[0][d][r] *= alpha;
+                    if (XL) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) st.ol[0][r] *= alpha;
+                    }
+                }
+                st.m[0] = mnew;
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sc[0][b][r] -= mnew;
+                st.fresh = false;
+                st.mz = false;
+            }
+            bool need = !BIAS && __any(xall > XTH);             // (BIAS: the lazy reference below is not used)
+            if (!BIAS && st.fresh) {
                 if (!LAZY0) {
                     need = true;
                 } else {                                  // reference 0 is fine unless a whole row sits below the head-room
@@ -863,6 +929,7 @@ __global__ __launch_bounds__(NW * 64) void aid_attn_kernel(const AttnKParams p) 
     auto init = [&](State& st) {
         st.fresh = true;
         st.mz = true;
+        st.bref = 0.f;
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
             st.m[j] = 0.f;

@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256, (D == 40 ? (TWO ? 2 : 3) : D == 64 ? 2 : D == 
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
         float mrow = -INFINITY, lsum = 0.f;                         // running reference and this lane half's partial row sum
+        float bref = -1e30f;                                        // score bias: its largest (clamped) value of the row so far
         const int ntl = (a.l + FKT - 1) / FKT;                      // tiles per segment
         const int nt = (k2 ? 2 : 1) * ntl;                          // (k1 is never null)
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -302,6 +303,15 @@ __global__ __launch_bounds__(256, (D == 40 ? (TWO ? 2 : 3) : D == 64 ? 2 : D == 
                     lstore(0);
                     __syncthreads();
                 }
+                if (brow) {                                        // the tile's largest bias per row, before the scores take their registers
+                    float bm = -1e30f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) bm = fmaxf(bm, brow[min(t0 + key_of(r, hi), a.l - 1)]);
+                    asm volatile("" ::: "memory");                 // (the loads below are issued again: 16 values are not kept live)
+                    const float bnew = fmaxf(bref, max_halves(bm));
+                    mrow += (bref - bnew) * 1.4426950408889634f;   // (-inf stays -inf: both references are finite)
+                    bref = bnew;
+                }
                 // S^T = K Q'^T: lane (query l31, half hi) receives the scores of keys key_of(r, hi)
                 f32x16 sc;
 #pragma unroll
@@ -312,10 +322,17 @@ __global__ __launch_bounds__(256, (D == 40 ? (TWO ? 2 : 3) : D == 64 ? 2 : D == 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) sc = mfma32f(kf[e], qf[4 * gq + e], sc);
                 }
-                if (brow) {                                        // scale q k^T + bias, in the log2 domain (values below -1e30 clamped, aid_attn.hip)
+                if (brow) {
+                    // scale q k^T + bias, in the log2 domain (values below -1e30 clamped).  The reference is bref (the largest bias
+                    // of the row so far) + mrow, and a key's bias enters as (bias - bref): exact where the two are equal, so a row
+                    // whose keys all carry -10000 keeps every bit of its q k (q k - 14427 in one fp32 would keep 2^-10 of it); the
+                    // cases are spelt out at the BIAS instantiation in aid_attn.hip.
 #pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        sc[r] += fmaxf(brow[min(t0 + key_of(r, hi), a.l - 1)], -1e30f) * 1.4426950408889634f;
+                    for (int r = 0; r < 16; ++r) {
+                        float db = fmaxf(brow[min(t0 + key_of(r, hi), a.l - 1)], -1e30f) - bref;
+                        asm volatile("" : "+v"(db));               // the difference first: -ffast-math may not spread it over the sum
+                        sc[r] += db * 1.4426950408889634f;
+                    }
                 }
                 float mx = -INFINITY;
 #pragma unroll

@@ -258,6 +258,7 @@ __global__ __launch_bounds__(256, (D == 40 ? 2 : D == 64 ? 2 : D == 80 ? (TWO ? 
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
         float mrow = -INFINITY, lsum = 0.f;                         // running reference and this lane half's partial row sum
+        float bref = -1e30f;                                        // score bias: its largest (clamped) value of the row so far
         const int ntl = (a.l + XKT - 1) / XKT;                      // tiles per segment
         const int nt = (k2 ? 2 : 1) * ntl;                          // (k1 is never null)
         f32x4 rk[NKC][2], rv[NVC][2];
@@ -343,6 +344,15 @@ __global__ __launch_bounds__(256, (D == 40 ? 2 : D == 64 ? 2 : D == 80 ? (TWO ? 
                 lstore(0);
                 __syncthreads();
             }
+            if (brow) {                                            // the tile's largest bias per row, before the scores take their registers
+                float bm = -1e30f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) bm = fmaxf(bm, brow[min(t0 + key_of_x3(r, hi), a.l - 1)]);
+                asm volatile("" ::: "memory");                     // (the loads below are issued again: 16 values are not kept live)
+                const float bnew = fmaxf(bref, max_halves(bm));
+                mrow += (bref - bnew) * 1.4426950408889634f;       // (-inf stays -inf: both references are finite)
+                bref = bnew;
+            }
             // S^T = K Q'^T, low-order terms first: lane (query l31, half hi) receives the scores of keys key_of_x3(r, hi)
             f32x16 sc;
 #pragma unroll
@@ -356,10 +366,15 @@ __global__ __launch_bounds__(256, (D == 40 ? 2 : D == 64 ? 2 : D == 80 ? (TWO ? 
                 sc = mfma32(kh, ql[g], sc);
                 sc = mfma32(kh, qh[g], sc);
             }
-            if (brow) {                                            // scale q k^T + bias, in the log2 domain (values below -1e30 clamped, aid_attn.hip)
+            if (brow) {
+                // scale q k^T + bias, in the log2 domain (values below -1e30 clamped), relative to the largest bias of the row so far
+                // like in aid_attn_f32_kernel (aid_f32.hip); the cases are spelt out at the BIAS instantiation in aid_attn.hip
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    sc[r] += fmaxf(brow[min(t0 + key_of_x3(r, hi), a.l - 1)], -1e30f) * 1.4426950408889634f;
+                for (int r = 0; r < 16; ++r) {
+                    float db = fmaxf(brow[min(t0 + key_of_x3(r, hi), a.l - 1)], -1e30f) - bref;
+                    asm volatile("" : "+v"(db));                   // the difference first: -ffast-math may not spread it over the sum
+                    sc[r] += db * 1.4426950408889634f;
+                }
             }
             float mx = -INFINITY;
 #pragma unroll

@@ -254,6 +254,18 @@ typedef struct AidAttnArgs {
     /* broadcast of an l-wide mask against 2 l scores.  INNER / OUTER apply it to the begin, end and interpolated segments       */
     /* alike.  Strides are multiples of 1 element; the base pointer needs the operand dtype's alignment only.  v7's kv_padded    */
     /* (a layout promise no kernel depended on) is gone.                                                                         */
+    /* Masks (values -10000, finfo.min, -inf; anything below -1e30 is read as -1e30).  Every kernel keeps the softmax reference   */
+    /* of a row as (largest bias seen so far) + (reference of the rest) and adds a key's bias as its difference to the former,   */
+    /* so the size of the mask value costs the scores of the live keys no bits:                                                  */
+    /*   masked key in a row with a live key    weight exactly 0 for all three values, wherever the two sit — same 64-key tile,   */
+    /*                                          an earlier or a later one;                                                        */
+    /*   tile whose keys are all masked         adds exact zeros after a tile with a live key; in front of the first live key     */
+    /*                                          (left padding, the first tiles of a row) it is accumulated and then cancelled     */
+    /*                                          exactly (factor 2^-14427 or smaller = 0) when the live key arrives.  No NaN;      */
+    /*   row whose keys are all masked          softmax(softmax_scale Q K^T) V over ALL its keys, for all three values: what the  */
+    /*                                          reference computes for -10000 and, up to its own rounding of score + finfo.min   */
+    /*                                          (uniform weights in fp16 / bf16), for finfo.min; for -inf the reference gives     */
+    /*                                          NaN and this finite row stands in.  The row is a convex combination of V's rows. */
     const void* bias;
     int64_t bias_fs;
     int32_t bias_hs, bias_rs;

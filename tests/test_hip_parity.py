@@ -377,8 +377,7 @@ def test_attention_core_with_score_bias(dtype, d):
     tol = 1e-5 if dtype == torch.float32 else TOL[dtype]
 
     def additive(*shape):
-        keep = torch.rand(*shape, generator=g) > 0.4
-        keep[..., 0] = True
+        keep = torch.rand(*shape, generator=g) > 0.4            # (masks with whole key tiles masked: test_hip_attn_mask_range.py)
         return ((1.0 - keep.float()) * -10000.0).to(dtype)
     for shape in ((n * h, 1, l), (n, 1, l), (n, h, s, l), (n, s, l)):
         m = additive(*shape)
