@@ -135,7 +135,9 @@ def test_memory_contract_on_guarded_buffers(dtype, d):
 
 
 # ---- processor ---------------------------------------------------------------------------------------------------------------------
-SHAPES = [(64, 320, 8, 64), (16, 1280, 20, 64)]         # (S, C, heads, Cc): d = 40 and d = 64
+# (S, C, heads, Cc): d = 40 and d = 64; the third has two workgroups per (frame, head) in the image-segment kernel, and its S = 160 takes
+# the zero-padding branch of the mask downsample (32 x 32 -> 13 x 12 = 156 < 160)
+SHAPES = [(64, 320, 8, 64), (16, 1280, 20, 64), (160, 128, 2, 64)]
 N, L = 3, 77
 
 
