@@ -9,7 +9,7 @@ Layout:  csrc/ (HIP kernels + C ABI, built to libaid_hip.so)  ·  _lib.py (ctype
 ops.py (tensor-level entry points)  ·  processors.py (the reference's AttnProcessor classes)  ·
 interp.py (coefficients, slerp / lerp initialisation)  ·  attn_shim.py (diffusers stand-ins)  ·
 dist.py (frame sharding over RCCL)  ·  loop.py (denoising-loop harness)  ·  sequence.py (batch assembly of
-interpolate_single / N-frame interpolate)  ·  endpoint_store.py (recorded end points: render further frames between them)  ·  pipelines.py (the reference's pipeline classes over components)  ·  prior.py (Beta-prior exploration of the coefficient path).
+interpolate_single / N-frame interpolate)  ·  endpoint_store.py (recorded end points: render further frames between them)  ·  keyframe_store.py (key frames recorded once: render between any two)  ·  pipelines.py (the reference's pipeline classes over components)  ·  prior.py (Beta-prior exploration of the coefficient path).
 """
 from .interp import generate_beta_tensor, linear_interpolation, slerp, spherical_interpolation
 from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
@@ -17,8 +17,9 @@ from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInter
                          OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, activate_aid,
                          clear_text_kv_cache, clear_weight_caches, deactivate_aid, load_aid, load_aid_ip_adapter)
 from .attn_shim import AttnShim, AttnStackUNet, IPAdapterShim
-from . import ops, _lib, sequence, loop, dist, prior, pipelines, endpoint_store
+from . import ops, _lib, sequence, loop, dist, prior, pipelines, endpoint_store, keyframe_store
 from .endpoint_store import EndpointStore
+from .keyframe_store import KeyframeStore
 from .ops import get_f32_attn_precision, set_f32_attn_precision
 from .prior import BetaPriorExplorer, BetaPriorPipeline
 from .pipelines import (DDIMSchedulerLite, InterpolationStableDiffusionPipeline,
@@ -32,6 +33,6 @@ __all__ = [
     "clear_text_kv_cache", "clear_weight_caches",
     "AttnShim", "AttnStackUNet", "IPAdapterShim", "ops", "set_f32_attn_precision", "get_f32_attn_precision",
     "BetaPriorPipeline", "BetaPriorExplorer", "InterpolationStableDiffusionPipeline", "InterpolationStableDiffusionXLPipeline", "DDIMSchedulerLite", "StackDenoiser",
-    "EndpointStore",
+    "EndpointStore", "KeyframeStore",
 ]
 __version__ = "0.1.0"

@@ -23,11 +23,15 @@ IP_NONE, IP_SAME, IP_PLAIN = 0, 1, 2
 IP_MAX_SEGMENTS = 8
 EP_PUT, EP_GET = 0, 1
 EP_RECORD, EP_REPLAY = 1, 2
+KF_MAX_ROWS = 8
+KF_PUT, KF_GET = 0, 1
+KF_RECORD, KF_REPLAY = 1, 2
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
     "aid_endpoint_rows", "aid_processor_ep_workspace_bytes", "aid_processor_ep_fwd",
+    "aid_keyframe_rows", "aid_processor_kf_workspace_bytes", "aid_processor_kf_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -128,6 +132,25 @@ class AidEndpointStore(C.Structure):
     ]
 
 
+class AidKeyframeRow(C.Structure):
+    _fields_ = [("k_store", C.c_void_p), ("vt_store", C.c_void_p), ("row", C.c_int32)]
+
+
+class AidKeyframeRows(C.Structure):
+    _fields_ = [
+        ("k", C.c_void_p), ("vt", C.c_void_p), ("rows", C.POINTER(AidKeyframeRow)), ("step", C.c_void_p),
+        ("k_fs", C.c_int64), ("vt_fs", C.c_int64),
+        ("n_rows", C.c_int32), ("n_steps", C.c_int32), ("direction", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
+class AidKeyframeCall(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(AidKeyframeRow)), ("step", C.c_void_p),
+        ("n_rows", C.c_int32), ("n_steps", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
 class AidProfileEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double),
                 ("flops_executed", C.c_double)]
@@ -204,6 +227,12 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_ep_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidEndpointStore)]
     lib.aid_processor_ep_fwd.restype = C.c_int
     lib.aid_processor_ep_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidEndpointStore), C.c_void_p]
+    lib.aid_keyframe_rows.restype = C.c_int
+    lib.aid_keyframe_rows.argtypes = [C.POINTER(AidKeyframeRows), C.c_void_p]
+    lib.aid_processor_kf_workspace_bytes.restype = C.c_size_t
+    lib.aid_processor_kf_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall)]
+    lib.aid_processor_kf_fwd.restype = C.c_int
+    lib.aid_processor_kf_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall), C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

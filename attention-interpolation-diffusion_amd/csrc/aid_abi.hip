@@ -633,6 +633,31 @@ int aid_endpoint_rows(const AidEndpointRows* args, void* stream) {
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_endpoint_rows");
 }
 
+int aid_keyframe_rows(const AidKeyframeRows* args, void* stream) {
+    if (!args) return AID_ERR_ARG;
+    const AidKeyframeRows& a = *args;
+    if (!a.k || !a.vt || !a.rows || !a.step || !aligned4(a.step)) return AID_ERR_ARG;
+    if (a.n_rows < 1 || a.n_rows > AID_KF_MAX_ROWS || a.n_steps < 1) return AID_ERR_ARG;
+    for (int i = 0; i < a.n_rows; ++i)
+        if (!a.rows[i].k_store || !a.rows[i].vt_store || a.rows[i].row < 0) return AID_ERR_ARG;
+    if (a.direction != AID_KF_PUT && a.direction != AID_KF_GET) return AID_ERR_ARG;
+    if (!dtype_ok(a.dtype)) return AID_ERR_DTYPE;
+    if (a.k_fs < 8 || a.vt_fs < 8 || a.k_fs % 8 || a.vt_fs % 8) return AID_ERR_SHAPE;
+    if (!aligned16(a.k) || !aligned16(a.vt)) return AID_ERR_SHAPE;
+    for (int i = 0; i < a.n_rows; ++i)
+        if (!aligned16(a.rows[i].k_store) || !aligned16(a.rows[i].vt_store)) return AID_ERR_SHAPE;
+    hipError_t e;
+    {
+        // traffic: the two blocks of every entry read once and written once
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_keyframe_rows<%s,%s>", dtype_name(a.dtype), a.direction == AID_KF_PUT ? "put" : "get");
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 0.0,
+                     (a.dtype == AID_DTYPE_F32 ? 4.0 : 2.0) * 2.0 * a.n_rows * (double)(a.k_fs + a.vt_fs));
+        e = aid::keyframe_rows_launch(a, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_keyframe_rows");
+}
+
 // end-point store beside a processor call (aid_hip.h): self-attention AID calls only
 static int check_endpoint_store(const AidProcessorArgs& a, const AidEndpointStore& ep) {
     if (ep.mode != AID_EP_RECORD && ep.mode != AID_EP_REPLAY) return AID_ERR_ARG;
@@ -642,8 +667,28 @@ static int check_endpoint_store(const AidProcessorArgs& a, const AidEndpointStor
     return AID_OK;
 }
 
+// key-frame stores beside a processor call (aid_hip.h): RECORD on a PLAIN self-attention call, REPLAY on an AID one
+static int check_keyframe_call(const AidProcessorArgs& a, const AidKeyframeCall& kf) {
+    if (kf.mode != AID_KF_RECORD && kf.mode != AID_KF_REPLAY) return AID_ERR_ARG;
+    if (a.ctx || a.ip) return AID_ERR_ARG;
+    if ((kf.mode == AID_KF_RECORD) != (a.mode == AID_MODE_PLAIN)) return AID_ERR_ARG;
+    if (!kf.rows || !kf.step || !aligned4(kf.step) || kf.n_steps < 1) return AID_ERR_ARG;
+    if (kf.mode == AID_KF_REPLAY ? kf.n_rows != 2 : (kf.n_rows < 1 || kf.n_rows > AID_KF_MAX_ROWS)) return AID_ERR_ARG;
+    for (int i = 0; i < kf.n_rows; ++i) {
+        if (!kf.rows[i].k_store || !kf.rows[i].vt_store) return AID_ERR_ARG;
+        if (kf.mode == AID_KF_RECORD) {
+            if (kf.rows[i].row < 0 || kf.rows[i].row >= a.n_frames) return AID_ERR_ARG;
+            for (int j = 0; j < i; ++j)
+                if (kf.rows[j].row == kf.rows[i].row) return AID_ERR_ARG;
+        }
+    }
+    for (int i = 0; i < kf.n_rows; ++i)
+        if (!aligned16(kf.rows[i].k_store) || !aligned16(kf.rows[i].vt_store)) return AID_ERR_SHAPE;
+    return AID_OK;
+}
+
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          void* stream);
+                          const AidKeyframeCall* kf, void* stream);
 
 size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidEndpointStore* ep) {
     if (!args) return 0;
@@ -654,21 +699,36 @@ size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidE
     return carve(a, ep->mode == AID_EP_REPLAY ? 2 : 0).total;
 }
 
-int aid_processor_fwd(const AidProcessorArgs* args, void* stream) { return processor_impl(args, nullptr, 0, nullptr, stream); }
+size_t aid_processor_kf_workspace_bytes(const AidProcessorArgs* args, const AidKeyframeCall* kf) {
+    if (!args) return 0;
+    if (!kf) return aid_processor_workspace_bytes(args);
+    AidProcessorArgs a = *args;
+    if (kf->mode == AID_KF_REPLAY) a.begin = a.end = 0;           // not read in replay
+    if (check_processor(a) != AID_OK || check_keyframe_call(a, *kf) != AID_OK) return 0;
+    return carve(a, kf->mode == AID_KF_REPLAY ? 2 : 0).total;
+}
+
+int aid_processor_fwd(const AidProcessorArgs* args, void* stream) { return processor_impl(args, nullptr, 0, nullptr, nullptr, stream); }
 
 int aid_processor_ip_fwd(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, void* stream) {
-    return processor_impl(args, ip_segs, n_ip_segs, nullptr, stream);
+    return processor_impl(args, ip_segs, n_ip_segs, nullptr, nullptr, stream);
 }
 
 int aid_processor_ep_fwd(const AidProcessorArgs* args, const AidEndpointStore* ep, void* stream) {
-    return processor_impl(args, nullptr, 0, ep, stream);
+    return processor_impl(args, nullptr, 0, ep, nullptr, stream);
 }
 
+int aid_processor_kf_fwd(const AidProcessorArgs* args, const AidKeyframeCall* kf, void* stream) {
+    return processor_impl(args, nullptr, 0, nullptr, kf, stream);
+}
+
+// ``ep`` / ``kf`` (at most one of them): which copy launch stands behind the projections — a pair store's aid_endpoint_rows or the
+// key-frame stores' aid_keyframe_rows.  Both replays are the same call: two rows more of k / V^T, filled by that launch.
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          void* stream) {
+                          const AidKeyframeCall* kf, void* stream) {
     if (!args) return AID_ERR_ARG;
     AidProcessorArgs a_local;
-    const bool replay = ep && ep->mode == AID_EP_REPLAY;
+    const bool replay = (ep && ep->mode == AID_EP_REPLAY) || (kf && kf->mode == AID_KF_REPLAY);
     if (replay) {                                         // the end points are rows n_frames / n_frames + 1 of k / V^T (filled from the
         a_local = *args;                                  // store below); args->begin / args->end are not read
         a_local.begin = a_local.end = 0;
@@ -678,6 +738,10 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
     if (rc != AID_OK) return rc;
     if (ep) {
         rc = check_endpoint_store(a, *ep);
+        if (rc != AID_OK) return rc;
+    }
+    if (kf) {
+        rc = check_keyframe_call(a, *kf);
         if (rc != AID_OK) return rc;
     }
     if (n_ip_segs < 0 || (n_ip_segs == 0 && ip_segs)) return AID_ERR_ARG;
@@ -840,6 +904,23 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         er.direction = replay ? AID_EP_GET : AID_EP_PUT;
         er.dtype = a.dtype;
         rc = aid_endpoint_rows(&er, stream);
+        if (rc != AID_OK) return rc;
+    }
+    if (kf) {                                                 // key-frame stores: the same two rows (REPLAY) / the key frames' rows (RECORD)
+        AidKeyframeRow two[2];
+        AidKeyframeRows kr;
+        memset(&kr, 0, sizeof(kr));
+        kr.k = ws + cv.k; kr.vt = ws + cv.vt; kr.rows = kf->rows; kr.n_rows = kf->n_rows;
+        if (replay) {
+            two[0] = kf->rows[0]; two[0].row = begin;
+            two[1] = kf->rows[1]; two[1].row = end;
+            kr.rows = two;
+        }
+        kr.step = kf->step; kr.n_steps = kf->n_steps;
+        kr.k_fs = (int64_t)l * a.c; kr.vt_fs = (int64_t)a.c * cv.lp;
+        kr.direction = replay ? AID_KF_GET : AID_KF_PUT;
+        kr.dtype = a.dtype;
+        rc = aid_keyframe_rows(&kr, stream);
         if (rc != AID_OK) return rc;
     }
 

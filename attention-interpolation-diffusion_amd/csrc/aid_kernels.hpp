@@ -202,6 +202,9 @@ hipError_t lerp_kv_launch(const void* k, const void* vt, void* k2, void* vt2, co
                           int end, int64_t k_fs, int64_t vt_fs, int dtype, hipStream_t stream);
 // end-point K / V^T rows between a call and slot *step of the end-point store (aid_endpoint.hip); arguments checked by the caller
 hipError_t endpoint_rows_launch(const AidEndpointRows& a, hipStream_t stream);
+// key-frame K / V^T rows between a call and slot *step of up to AID_KF_MAX_ROWS key-frame stores (aid_keyframe.hip); arguments checked
+// by the caller
+hipError_t keyframe_rows_launch(const AidKeyframeRows& a, hipStream_t stream);
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,
                             int dtype, hipStream_t stream);
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);

@@ -54,7 +54,39 @@ def lora_state(unet) -> Tuple:
     return tuple(out)
 
 
-class EndpointStore:
+class StepIndex:
+    """The device step index of a store (shared with keyframe_store.KeyframeStore): ONE int32 on the device that the copy kernels read,
+    and its host copy.  The owner sets ``n_steps``."""
+
+    _step: Optional[torch.Tensor] = None
+    step = -1                                      # host copy of the device index
+    n_steps = 0
+
+    def _ensure_step(self, device: torch.device) -> None:
+        if self._step is None or self._step.device != torch.device(device):
+            self._step = torch.zeros(1, dtype=torch.int32, device=device)
+            self.step = 0
+
+    @property
+    def step_tensor(self) -> torch.Tensor:
+        return self._step
+
+    def set_step(self, i: int) -> None:
+        """Name the AID step the next calls record into / replay from: ONE int32 on the device rewritten in place, stream-ordered
+        and outside the captured graphs (as ``activate(t)`` rewrites the coefficient buffers) — a replayed graph reads the live index."""
+        i = int(i)
+        if not 0 <= i < max(self.n_steps, 1):
+            raise IndexError(f"step {i} outside the store's {self.n_steps} AID steps")
+        if self._step is None:
+            raise RuntimeError("set_step before the run began (begin_record / begin_replay)")
+        if self._step.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_step inside a stream capture: the index is rewritten between replays, not inside the graph")
+        if i != self.step:
+            self._step.fill_(i)
+            self.step = i
+
+
+class EndpointStore(StepIndex):
     """See the module docstring.  ``max_bytes``: a record that would need more raises ``ValueError`` naming the bytes needed, before
     the buffer that crosses the limit is allocated — and what the refused record had allocated so far is dropped, so nothing of it
     stays.  One store serves one pair of end points; ``clear()`` empties it for another."""
@@ -126,30 +158,6 @@ class EndpointStore:
                                  f"and under the settings it was recorded with (recorded {_short(self.signature.get(f))}, this run "
                                  f"{_short(signature.get(f))}); clear() it to record again")
 
-    # -- the device step index --------------------------------------------------------------------------------------------------
-    def _ensure_step(self, device: torch.device) -> None:
-        if self._step is None or self._step.device != torch.device(device):
-            self._step = torch.zeros(1, dtype=torch.int32, device=device)
-            self.step = 0
-
-    @property
-    def step_tensor(self) -> torch.Tensor:
-        return self._step
-
-    def set_step(self, i: int) -> None:
-        """Name the AID step the next calls record into / replay from: ONE int32 on the device rewritten in place, stream-ordered
-        and outside the captured graphs (as ``activate(t)`` rewrites the coefficient buffers) — a replayed graph reads the live index."""
-        i = int(i)
-        if not 0 <= i < max(self.n_steps, 1):
-            raise IndexError(f"step {i} outside the store's {self.n_steps} AID steps")
-        if self._step is None:
-            raise RuntimeError("set_step before the run began (begin_record / begin_replay)")
-        if self._step.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("set_step inside a stream capture: the index is rewritten between replays, not inside the graph")
-        if i != self.step:
-            self._step.fill_(i)
-            self.step = i
-
     # -- per-layer buffers ------------------------------------------------------------------------------------------------------
     def _refuse_over(self, need: int) -> None:
         if self.max_bytes is not None and need > self.max_bytes:
@@ -192,22 +200,31 @@ def _short(v) -> str:
     return s if len(s) <= 24 else s[:21] + "..."
 
 
+def run_settings(*, num_inference_steps: int, guidance_scale: float, dtype: torch.dtype, timesteps, unet, lora_scale=None) -> Dict[str, Any]:
+    """The settings of a run that an end point's own trajectory depends on (shared with keyframe_store.py): the settings themselves,
+    the float32 precision codes in force, the LoRA adapters' state and the identity of the UNet."""
+    ts = timesteps.detach().to("cpu").tolist() if torch.is_tensor(timesteps) else [float(t) for t in timesteps]
+    return {
+        "num_inference_steps": int(num_inference_steps), "guidance_scale": float(guidance_scale), "dtype": str(dtype),
+        "f32_precision": (ops.f32_split_code(), ops.f32_attn_split_code()) if dtype == torch.float32 else (0, 0),
+        "timesteps": tuple(ts), "lora": (lora_state(unet), None if lora_scale is None else float(lora_scale)),
+        "unet": (type(unet).__name__, id(unet)),
+    }
+
+
 def run_signature(*, latent_start, latent_end, embeds_start, embeds_end, embeds_negative: List[Optional[torch.Tensor]],
                   embeds_pooled: List[Optional[torch.Tensor]], embeds_guide: List[Optional[torch.Tensor]], num_inference_steps: int,
                   warmup_ratio: float, early: str, late: str, fusion: bool, guidance_scale: float, dtype: torch.dtype, timesteps,
                   unet, lora_scale=None) -> Dict[str, Any]:
     """The signature a pipeline run records / replays under (``SIGNATURE_FIELDS``): content digests of the tensors, the settings
     themselves, the float32 precision codes in force, the LoRA adapters' state and the identity of the UNet."""
-    ts = timesteps.detach().to("cpu").tolist() if torch.is_tensor(timesteps) else [float(t) for t in timesteps]
-    return {
+    sig = {
         "latent_start": tensor_digest(latent_start), "latent_end": tensor_digest(latent_end),
         "embeds_start": tensor_digest(embeds_start), "embeds_end": tensor_digest(embeds_end),
         "embeds_negative": tensor_digest(*embeds_negative), "embeds_pooled": tensor_digest(*embeds_pooled),
-        "embeds_guide": tensor_digest(*embeds_guide),
-        "num_inference_steps": int(num_inference_steps), "warmup_ratio": float(warmup_ratio),
-        "early": str(early), "late": str(late), "fusion": bool(fusion), "guidance_scale": float(guidance_scale),
-        "dtype": str(dtype),
-        "f32_precision": (ops.f32_split_code(), ops.f32_attn_split_code()) if dtype == torch.float32 else (0, 0),
-        "timesteps": tuple(ts), "lora": (lora_state(unet), None if lora_scale is None else float(lora_scale)),
-        "unet": (type(unet).__name__, id(unet)),
+        "embeds_guide": tensor_digest(*embeds_guide), "warmup_ratio": float(warmup_ratio),
+        "early": str(early), "late": str(late), "fusion": bool(fusion),
+        **run_settings(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, dtype=dtype, timesteps=timesteps,
+                       unet=unet, lora_scale=lora_scale),
     }
+    return {f: sig[f] for f in SIGNATURE_FIELDS}

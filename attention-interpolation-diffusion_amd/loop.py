@@ -93,6 +93,38 @@ def set_endpoint_store(unet, store, endpoint_ctx: Optional[torch.Tensor] = None,
                 proc.coef = torch.as_tensor(coef, dtype=torch.float32).detach().cpu().clone()
 
 
+def set_keyframe_store(unet, store, record: Optional[Sequence[str]] = None, between: Optional[Tuple[str, str]] = None,
+                       endpoint_ctx: Optional[torch.Tensor] = None, coef=None) -> None:
+    """Attach a ``KeyframeStore`` (keyframe_store.py) to every AID processor of ``unet`` for one pass or run — or detach it
+    (``store=None``).  ``record=[names]``: the store is recording those frames (``begin_record``), the processors' plain self-attention
+    calls put rows 0 .. K-1 of their batch into them.  ``between=(a, b)``: the store is replaying that pair (``between(a, b).begin_replay``),
+    ``endpoint_ctx`` [2, L, Cc] holds the two frames' text contexts for the cross-attention calls and ``coef`` the interior
+    coefficients, as in ``set_endpoint_store``.  A processor holds either kind of store, never both; IP-Adapter processors refuse a
+    store at their first call."""
+    if store is not None:
+        if (record is None) == (between is None):
+            raise ValueError("set_keyframe_store takes record=[names] or between=(a, b)")
+        want = "record" if record is not None else "replay"
+        if store.mode != want:
+            raise RuntimeError(f"the key-frame store is not in a {want} run (begin_record / between(a, b).begin_replay come first)")
+        if record is not None and list(record) != list(store._pending):
+            raise ValueError(f"the store is recording {list(store._pending)}, not {list(record)}")
+        if between is not None and tuple(between) != tuple(store._pair):
+            raise ValueError(f"the store is replaying {tuple(store._pair)}, not {tuple(between)}")
+    for name, proc in unet.attn_processors.items():
+        if isinstance(proc, InterpolatedAttnProcessor):
+            if store is not None and getattr(proc, "endpoint_store", None) is not None:
+                raise RuntimeError("the processor holds an end-point store: a processor takes an EndpointStore or a KeyframeStore, "
+                                   "not both (set_endpoint_store(unet, None) first)")
+            had = getattr(proc, "keyframe_store", None) is not None
+            proc.keyframe_store = store
+            if store is not None or had:
+                proc.endpoint_layer = name if store is not None else None
+                proc.endpoint_ctx = endpoint_ctx
+            if coef is not None:
+                proc.coef = torch.as_tensor(coef, dtype=torch.float32).detach().cpu().clone()
+
+
 def _record_stream(out, stream) -> None:
     if torch.is_tensor(out):
         out.record_stream(stream)

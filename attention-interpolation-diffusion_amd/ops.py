@@ -16,13 +16,17 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME, MODE_INNER, MODE_OUTER, MODE_PLAIN,
-                   AidAttnArgs, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidProcessorArgs)
+from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME,
+                   KF_GET, KF_MAX_ROWS, KF_PUT, KF_RECORD, KF_REPLAY, MODE_INNER, MODE_OUTER, MODE_PLAIN,
+                   AidAttnArgs, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeCall,
+                   AidKeyframeRow, AidKeyframeRows, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
 IP_MODES = {"same": IP_SAME, "plain": IP_PLAIN}
 EP_MODES = {"record": EP_RECORD, "replay": EP_REPLAY}
 EP_DIRECTIONS = {"put": EP_PUT, "get": EP_GET}
+KF_MODES = {"record": KF_RECORD, "replay": KF_REPLAY}
+KF_DIRECTIONS = {"put": KF_PUT, "get": KF_GET}
 SUPPORTED_HEAD_DIMS = (40, 64, 80, 160)
 
 
@@ -652,7 +656,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None,
                   f32_attn_precision: Optional[str] = None, ip_segments: Optional[Sequence[dict]] = None,
-                  ep: Optional[dict] = None) -> torch.Tensor:
+                  ep: Optional[dict] = None, kf: Optional[dict] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -678,7 +682,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     ``ip_segments``: image-key segments (``ip_attn_accumulate``'s dicts; ``aid_processor_ip_fwd``) added to the attention output in
     one launch after the text attention — several IP-Adapters per layer, regional masks as ``row_weight``.  A cross-attention
     ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only.
-    ``ep``: the end-point store of the layer, see ``processor_ep_fwd``."""
+    ``ep``: the end-point store of the layer, see ``processor_ep_fwd``.  ``kf``: key-frame stores of the layer, see
+    ``processor_kf_fwd`` (one of the two at most)."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
     attn_split = f32_attn_split_code(f32_attn_precision)
@@ -792,12 +797,19 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     if dt == DTYPE_F32:
         a.f32_split = split
         a.f32_attn_split = attn_split
-    est = None
+    est = kcall = None
+    if ep is not None and kf is not None:
+        raise ValueError("a call takes an end-point store (ep=) or key-frame stores (kf=), not both")
     if ep is not None:
         if seg_arr is not None:
             raise ValueError("an end-point store belongs to a self-attention call: no ip_segments")
         est = _endpoint_store_args(ep, s, c, x.dtype)
         nbytes = lib.aid_processor_ep_workspace_bytes(C.byref(a), C.byref(est))
+    elif kf is not None:
+        if seg_arr is not None:
+            raise ValueError("key-frame stores belong to a self-attention call: no ip_segments")
+        kcall, _kf_rows = _keyframe_call_args(kf, n, s, c, x.dtype)          # (_kf_rows: the host array kcall points at, kept alive)
+        nbytes = lib.aid_processor_kf_workspace_bytes(C.byref(a), C.byref(kcall))
     else:
         nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):
@@ -806,6 +818,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
             a.workspace, a.workspace_bytes = None, 0
             if est is not None:
                 _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
+            elif kcall is not None:
+                _lib.check(lib.aid_processor_kf_fwd(C.byref(a), C.byref(kcall), _stream()), "aid_processor_kf_fwd")
             else:
                 _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
             raise RuntimeError("aid_processor_workspace_bytes returned 0")
@@ -813,6 +827,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
         if est is not None:
             _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
+        elif kcall is not None:
+            _lib.check(lib.aid_processor_kf_fwd(C.byref(a), C.byref(kcall), _stream()), "aid_processor_kf_fwd")
         elif seg_arr is not None:
             _lib.check(lib.aid_processor_ip_fwd(C.byref(a), C.addressof(seg_arr), len(seg_arr), _stream()), "aid_processor_ip_fwd")
         else:
@@ -894,3 +910,91 @@ def processor_ep_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
     if kwargs.get("mode", "plain") == "plain":
         raise ValueError("an end-point store belongs to an interpolated (inner / outer) call")
     return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, ep=ep, **kwargs)
+
+
+# ---- key-frame K / V^T stores (aid_hip.h: aid_keyframe_rows, aid_processor_kf_fwd) --------------------------------------------------
+def _keyframe_row_array(entries, step: torch.Tensor, k_fs: int, vt_fs: int, dtype: torch.dtype):
+    """The host array of AidKeyframeRow for ``entries`` = [(k_store [n_steps, k_fs], vt_store [n_steps, vt_fs], row), ...]; returns
+    (array, n_steps).  Every key frame's store is its own allocation; all hold the same number of steps."""
+    entries = list(entries)
+    if not 1 <= len(entries) <= KF_MAX_ROWS:
+        raise ValueError(f"one launch moves 1 .. {KF_MAX_ROWS} key-frame rows; got {len(entries)}")
+    arr = (AidKeyframeRow * len(entries))()
+    n_steps = None
+    for i, (k_store, vt_store, row) in enumerate(entries):
+        _require_gpu(k_store, vt_store)
+        if k_store.dtype != dtype or vt_store.dtype != dtype:
+            raise TypeError(f"the key-frame store holds {k_store.dtype}, the call computes in {dtype}")
+        ns = k_store.shape[0]
+        if k_store.ndim != 2 or vt_store.ndim != 2 or tuple(k_store.shape) != (ns, k_fs) or tuple(vt_store.shape) != (ns, vt_fs) \
+                or not k_store.is_contiguous() or not vt_store.is_contiguous() or ns < 1:
+            raise ValueError(f"a key-frame store must be k_store [n_steps, {k_fs}] / vt_store [n_steps, {vt_fs}], contiguous; got "
+                             f"{tuple(k_store.shape)} / {tuple(vt_store.shape)}")
+        if n_steps is not None and ns != n_steps:
+            raise ValueError(f"the key-frame stores of one launch hold the same number of steps; got {n_steps} and {ns}")
+        n_steps = ns
+        arr[i].k_store, arr[i].vt_store, arr[i].row = k_store.data_ptr(), vt_store.data_ptr(), int(row)
+    _require_gpu(step)
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise ValueError("the step index is ONE int32 on the device (rewritten in place between calls)")
+    return arr, n_steps
+
+
+def _keyframe_call_args(kf: dict, n_frames: int, l: int, c: int, dtype: torch.dtype):
+    k_fs, vt_fs = endpoint_block_sizes(l, c)
+    try:
+        mode = KF_MODES[kf["mode"]]
+    except (KeyError, TypeError):
+        raise ValueError(f"kf['mode'] must be 'record' or 'replay'; got {kf.get('mode')!r}") from None
+    entries = [(k_, v_, int(r_) % n_frames if mode == KF_RECORD else 0) for k_, v_, r_ in kf["entries"]]
+    if mode == KF_REPLAY and len(entries) != 2:
+        raise ValueError(f"a replay takes exactly two key-frame stores (begin, end); got {len(entries)}")
+    if mode == KF_RECORD and len({r_ for _, _, r_ in entries}) != len(entries):
+        raise ValueError("the recorded rows must be distinct")
+    arr, n_steps = _keyframe_row_array(entries, kf["step"], k_fs, vt_fs, dtype)
+    call = AidKeyframeCall()
+    call.rows, call.step, call.n_rows, call.n_steps, call.mode = arr, kf["step"].data_ptr(), len(arr), n_steps, mode
+    return call, arr
+
+
+def keyframe_rows(k: torch.Tensor, vt: torch.Tensor, entries, step: torch.Tensor, direction: str) -> None:
+    """Move rows between a call's k [F, L, C] / vt [F, C, Lp] and slot ``step[0]`` of up to 8 key-frame stores in one launch
+    (``aid_keyframe_rows``).  ``entries`` = [(k_store [n_steps, L C], vt_store [n_steps, C Lp], row), ...], each store its own
+    allocation; ``direction`` "put" = call -> store, "get" = store -> call.  ``step`` is ONE int32 on the device, read by the kernel; an
+    index outside the stores moves nothing."""
+    dev = _require_gpu(k, vt)
+    if k.dtype != vt.dtype or k.ndim != 3 or vt.ndim != 3 or not k.is_contiguous() or not vt.is_contiguous() or k.shape[0] != vt.shape[0]:
+        raise ValueError("k [F, L, C] and vt [F, C, Lp] must be contiguous tensors of one dtype with the same number of rows")
+    f = k.shape[0]
+    a = AidKeyframeRows()
+    a.k_fs, a.vt_fs = k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2]
+    arr, a.n_steps = _keyframe_row_array([(k_, v_, int(r_) % f) for k_, v_, r_ in entries], step, a.k_fs, a.vt_fs, k.dtype)
+    a.k, a.vt, a.rows, a.step, a.n_rows = k.data_ptr(), vt.data_ptr(), arr, step.data_ptr(), len(arr)
+    try:
+        a.direction = KF_DIRECTIONS[direction]
+    except (KeyError, TypeError):
+        raise ValueError(f"direction must be 'put' or 'get'; got {direction!r}") from None
+    a.dtype = _dtype_code(k)
+    with _on(dev):
+        _lib.check(_lib.load().aid_keyframe_rows(C.byref(a), _stream()), "aid_keyframe_rows")
+
+
+def processor_kf_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, wo: torch.Tensor,
+                     bo: Optional[torch.Tensor], heads: int, *, kf: dict, **kwargs) -> torch.Tensor:
+    """A SELF-attention processor call with key-frame stores of its layer beside it (``aid_processor_kf_fwd``) — still one library
+    call.  ``kf`` = dict(entries=[(k_store [n_steps, S C], vt_store [n_steps, C round_up(S, 8)], row), ...], step=int32 device [1],
+    mode="record" | "replay"); every other keyword is ``processor_fwd``'s.
+    "record": a ``mode="plain"`` call over a batch that holds the key frames — ``processor_fwd`` itself, ``y`` bit for bit — plus rows
+    ``row`` of this step's k / V^T put into slot ``step[0]`` of their stores (1 .. 8 entries, distinct rows).  "replay": an
+    interpolated call; ``x`` holds the LOCAL frames only (interior coefficients, PLAIN riders), the two entries are the begin and the
+    end frame's stores (``row`` is ignored, ``begin`` / ``end`` are not read); swapped, the call renders the reverse direction."""
+    if kf is None:
+        raise ValueError("processor_kf_fwd needs the layer's key-frame stores (kf=...); without them call processor_fwd")
+    if kwargs.get("ip") is not None or kwargs.get("ip_segments") or kwargs.get("kv_cached") is not None or kwargs.get("ctx_map") is not None:
+        raise ValueError("key-frame stores belong to a self-attention call: no image branch, no cached text keys, no ctx_map")
+    plain = kwargs.get("mode", "plain") == "plain"
+    if kf.get("mode") == "record" and not plain:
+        raise ValueError("key frames are recorded from a plain call (mode='plain'): an end point's trajectory is plain attention")
+    if kf.get("mode") == "replay" and plain:
+        raise ValueError("key-frame stores replay into an interpolated (inner / outer) call")
+    return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, kf=kf, **kwargs)

@@ -37,15 +37,18 @@ import warnings
 
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 from torch import nn
 
 from . import ops
 from . import processors as P
+from ._lib import KF_MAX_ROWS
 from .attn_shim import AttnStackUNet
 from .interp import generate_beta_tensor, linear_interpolation, slerp, spherical_interpolation
-from .endpoint_store import EndpointStore, run_signature
-from .loop import EARLY_MODES, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store
+from .endpoint_store import EndpointStore, run_settings, run_signature
+from .keyframe_store import KeyframePair, KeyframeStore
+from .loop import EARLY_MODES, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store, set_keyframe_store
 from .sequence import SequenceBatch, prepare_sequence, prepare_single
 
 
@@ -608,7 +611,9 @@ class InterpolationStableDiffusionPipeline:
             for mode in {early} | ({late} - {"self"}):
                 install_sequence_processors(self.unet, size, early=mode, alpha=alpha, beta=beta,
                                             num_inference_steps=num_inference_steps, coef=run_coef)
-                if ep_mode is not None:
+                if isinstance(endpoints, KeyframePair):      # (interpolate_between: the pair's two frames of a KeyframeStore)
+                    set_keyframe_store(self.unet, endpoints.store, between=(endpoints.a, endpoints.b), endpoint_ctx=ectx)
+                elif ep_mode is not None:
                     set_endpoint_store(self.unet, endpoints, endpoint_ctx=ectx)
                 procs[mode] = dict(self.unet.attn_processors)
             graphs = _PassGraphs(_use_graphs(use_graphs, dev))
@@ -659,6 +664,134 @@ class InterpolationStableDiffusionPipeline:
             set_ctx_index(self.unet, None)
             self.unet.set_attn_processor(installed)
         return self._decode(lat, output_type)
+
+    # -- key frames: record once, render between any two --------------------------------
+    @torch.no_grad()
+    def record_keyframes(self, store: KeyframeStore, names: Sequence[str], latents, prompts: Optional[Sequence[str]] = None,
+                         embeds: Optional[Sequence[tuple]] = None, negative_prompt: str = "", num_inference_steps: int = 25,
+                         warmup_ratio: float = 0.5, aid_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
+                         use_graphs: Optional[bool] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
+                         output_type: str = "np"):
+        """Denoise the K key frames ``names`` as ONE plain classifier-free-guidance batch (``latents`` [K, C, h, w] or K tensors
+        [1, C, h, w]; ``prompts`` or ``embeds``, one per frame, as ``interpolate`` takes ``prompt_start`` / ``embeds_start``) and record
+        them into ``store``: at every self-attention layer of the conditional pass of the first ``aid_steps`` steps (default
+        ``int(num_inference_steps * warmup_ratio)``; pass ``num_inference_steps`` to allow ``late`` AID modes) each frame's k / V^T
+        goes into its own store — one PUT launch beside the projections — and each frame's inputs and final latent are kept.  That is
+        everything ``interpolate_between`` needs of a frame, whichever partner, direction or early mode it is rendered with.  A
+        name the store already holds raises; further frames may be recorded later under the same settings.  More than 8 frames
+        (``AID_KF_MAX_ROWS``, what one launch moves) are recorded in runs of up to 8.  Returns the decoded key frames."""
+        names = [str(n) for n in names]
+        k = len(names)
+        lats = [latents[i:i + 1] for i in range(k)] if torch.is_tensor(latents) else list(latents)
+        for what, seq in (("latents", lats), ("prompts", prompts), ("embeds", embeds)):
+            if seq is not None and len(seq) != k:
+                raise ValueError(f"record_keyframes needs one entry of {what} per name: {len(seq)} for {k} names")
+        if len(set(names)) != k:
+            raise ValueError(f"record_keyframes needs distinct names, one per frame; got {names}")
+        for n in names:
+            if n in store:
+                raise ValueError(f"key frame {n!r} is already recorded: remove({n!r}) it first")
+        if k > KF_MAX_ROWS:
+            outs = []
+            for g0 in range(0, k, KF_MAX_ROWS):
+                sl = slice(g0, g0 + KF_MAX_ROWS)
+                outs.append(self.record_keyframes(store, names[sl], lats[sl], None if prompts is None else prompts[sl],
+                                                  None if embeds is None else embeds[sl], negative_prompt, num_inference_steps,
+                                                  warmup_ratio, aid_steps, guidance_scale, use_graphs, cross_attention_kwargs, output_type))
+            return torch.cat(outs) if torch.is_tensor(outs[0]) else np.concatenate(outs)
+        gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
+        dev, dtype = self._unet_device_dtype()
+        cak = cross_attention_kwargs
+        ls = cak.get("scale", None) if cak is not None else None
+        embs = [self._embed(None if prompts is None else prompts[i], negative_prompt, None if embeds is None else embeds[i], ls)
+                for i in range(k)]
+        sides = [self._split(e) for e in embs]
+        cond = torch.cat([s_[0][0] for s_ in sides]).to(dev, dtype).contiguous()
+        unc = torch.cat([s_[1][0] for s_ in sides]).to(dev, dtype).contiguous()
+        pooled = (torch.cat([s_[0][1] for s_ in sides]), torch.cat([s_[1][1] for s_ in sides])) if len(sides[0][0]) > 1 else None
+        lat0 = torch.cat([l_.to(dev, dtype) for l_ in lats])
+        self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        n_aid = int(num_inference_steps * warmup_ratio) if aid_steps is None else int(aid_steps)
+        if not 1 <= n_aid <= num_inference_steps:
+            raise ValueError(f"aid_steps must be in 1 .. num_inference_steps ({num_inference_steps}); got {n_aid}")
+        settings = run_settings(num_inference_steps=num_inference_steps, guidance_scale=gs, dtype=dtype,
+                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls)
+        installed = dict(self.unet.attn_processors)          # restored at the end, as interpolate does
+        store.begin_record(names, settings, n_aid, dev)
+        try:
+            # plain attention through the AID processors' own plain path (no wrapped original): the call that takes the store
+            P.clear_weight_caches()
+            procs = {}
+            for name in installed:
+                procs[name] = P.OuterInterpolatedAttnProcessor(size=2, original_attn=None)
+                procs[name].activated = False
+            self.unet.set_attn_processor(procs)
+            set_ctx_index(self.unet, None)
+            graphs = _PassGraphs(_use_graphs(use_graphs, dev))
+            added_c = self._added_cond(None if pooled is None else pooled[0], k)
+            added_u = self._added_cond(None if pooled is None else pooled[1], k)
+
+            def cond_pass(x, t):
+                return self._unet(x, t, cond, added_c, cak)
+
+            def uncond_pass(x, t):
+                return self._unet(x, t, unc, added_u, cak)
+
+            lat = lat0
+            for i, t in enumerate(self.scheduler.timesteps):
+                x = self.scheduler.scale_model_input(lat, t)
+                td = _dev_scalar(t, dev) if graphs.enabled else t
+                rec = i < n_aid
+                if rec:                                       # the conditional pass of an AID step is what a later pair attends to
+                    set_keyframe_store(self.unet, store, record=names)
+                    store.set_step(i)
+                noise_text = graphs.run(("cond", rec), cond_pass, x=x, t=td)
+                set_keyframe_store(self.unet, None)
+                noise_unc = graphs.run(("uncond",), uncond_pass, x=x, t=td)
+                noise = noise_unc + gs * (noise_text - noise_unc)
+                lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
+            store.finish_record(lat0, embs, lat)
+        finally:
+            store.abort()                        # (no-op after finish_record; a failed recording leaves nothing of itself behind)
+            set_ctx_index(self.unet, None)
+            self.unet.set_attn_processor(installed)
+        return self._decode(lat, output_type)
+
+    def interpolate_between(self, store: KeyframeStore, a: str, b: str, size: int = 7, coef: Optional[Sequence[float]] = None,
+                            guide_prompt: Optional[str] = None, embeds_guide=None, negative_prompt: str = "",
+                            early: str = "fused_outer", late: str = "self", warmup_ratio: float = 0.5,
+                            alpha: Optional[float] = None, beta: Optional[float] = None, batched_cfg: bool = True,
+                            output_type: str = "np", use_graphs: Optional[bool] = None,
+                            num_inference_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
+                            cross_attention_kwargs: Optional[Dict[str, Any]] = None):
+        """Render ``size`` frames from key frame ``a`` to key frame ``b`` of ``store``: the ``size - 2`` interior frames go through the
+        UNet exactly as in an ``interpolate(..., endpoints=<recorded store>)`` replay — latents and embeddings of the two frames come
+        from the store, their AID steps attend to the frames' recorded keys / values — and the two end frames are the stored final
+        latents.  ``(b, a)`` renders the reverse direction from the same recordings; any ``early`` mode does.  ``num_inference_steps``
+        / ``guidance_scale`` default to the store's.  An unknown name raises ``KeyError``; a run that needs more AID steps than were
+        recorded, or whose step count, guidance scale, dtype, timesteps, UNet or LoRA state differ from the recording's, raises
+        ``ValueError`` naming what differs."""
+        fa, fb = store[a], store[b]
+        pair = store.between(a, b)
+        steps = store.settings["num_inference_steps"] if num_inference_steps is None else num_inference_steps
+        gs = store.settings["guidance_scale"] if guidance_scale is None else guidance_scale
+        return self.interpolate(fa.latent, fb.latent, guide_prompt=guide_prompt, negative_prompt=negative_prompt, size=size,
+                                num_inference_steps=steps, warmup_ratio=warmup_ratio, early=early, late=late, alpha=alpha, beta=beta,
+                                guidance_scale=gs, embeds_start=fa.embeds, embeds_end=fb.embeds, embeds_guide=embeds_guide,
+                                batched_cfg=batched_cfg, output_type=output_type, coef=coef, use_graphs=use_graphs,
+                                cross_attention_kwargs=cross_attention_kwargs, endpoints=pair)
+
+    def interpolate_chain(self, store: KeyframeStore, names: Sequence[str], size: int = 7, **kwargs):
+        """``interpolate_between`` for every consecutive pair of ``names``, in order, joined with each shared key frame once:
+        ``(K - 1) (size - 1) + 1`` frames for K names.  ``kwargs`` are ``interpolate_between``'s."""
+        names = list(names)
+        if len(names) < 2:
+            raise ValueError("a chain needs at least two key frames")
+        for n in names:
+            store[n]
+        parts = [self.interpolate_between(store, names[i], names[i + 1], size=size, **kwargs) for i in range(len(names) - 1)]
+        parts = parts[:1] + [p_[1:] for p_ in parts[1:]]
+        return torch.cat(parts) if torch.is_tensor(parts[0]) else np.concatenate(parts)
 
     # -- small shape helpers (overridden by the XL class) ----------------------------------------------
     def _installed_aid_mode(self):

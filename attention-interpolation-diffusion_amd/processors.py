@@ -76,6 +76,11 @@ class InterpolatedAttnProcessor(nn.Module):
         # this processor's layer in the store, ``endpoint_ctx`` serves the cross-attention calls of a replay as above.
         self.endpoint_store = None
         self.endpoint_layer: Optional[str] = None
+        # build-specific: ``keyframe_store`` (keyframe_store.KeyframeStore, set by ``loop.set_keyframe_store``) keeps
+        # ONE recording per key frame.  Recording, the PLAIN self-attention calls of a batch of key frames put their rows into the
+        # frames' stores; replaying, an AID call reads the two frames of a pair from there exactly as from a replaying
+        # ``endpoint_store`` (``endpoint_layer`` / ``endpoint_ctx`` serve both).  A processor holds one kind of store, never both.
+        self.keyframe_store = None
 
     # ``coef`` stays a plain CPU tensor attribute like the reference's (interpolation.py:21-27, 42); assigning it
     # (``activate(t)``, ``proc.coef = ...``) refreshes the device copies at once, so a replayed graph never sees the
@@ -429,22 +434,39 @@ def _run_text(proc: InterpolatedAttnProcessor, attn, hidden_states, encoder_hidd
     ctx_index = proc.ctx_index if ctx_index is None else ctx_index
     exchange = getattr(proc, "endpoint_exchange", None)
     store = getattr(proc, "endpoint_store", None) if mode != "plain" else None
+    kstore = getattr(proc, "keyframe_store", None)
+    if kstore is not None:
+        if getattr(proc, "endpoint_store", None) is not None:
+            raise NotImplementedError("an end-point store and a key-frame store on one processor: a processor holds one kind of store")
+        if kstore.mode == "record" and mode != "plain":
+            raise RuntimeError("key frames are recorded by a plain batch (de-activated processors): an end point's trajectory is "
+                               "plain attention of that frame")
+        if kstore.mode is None:
+            raise RuntimeError("the key-frame store is attached to a processor outside a run (record_keyframes / interpolate_between)")
+        # recording: the plain calls; replaying: the AID calls (the plain passes of a replaying run need nothing of it)
+        store = kstore if (kstore.mode == "record") == (mode == "plain") else None
+    kind = "a key-frame store" if kstore is not None else "an end-point store"
     replay = store is not None and store.mode == "replay"
     if store is not None:
         if exchange is not None:
-            raise NotImplementedError("an end-point store together with endpoint_exchange: the store replays recorded end points in "
+            raise NotImplementedError(f"{kind} together with endpoint_exchange: the store replays recorded end points in "
                                       "a single-device batch, the exchange fetches live ones from their owner ranks — use one")
         if not x.is_cuda:
-            raise NotImplementedError("an end-point store on a CPU tensor: the store lives in device memory and is read by the HIP "
+            raise NotImplementedError(f"{kind} on a CPU tensor: the store lives in device memory and is read by the HIP "
                                       "kernels (there is no CPU path)")
         if ctx is None:                               # self-attention: one library call with the layer's store beside it
-            fused = proc.is_fused
-            ep = store.ep_args(proc.endpoint_layer or f"layer@{id(attn):x}", x.shape[1], x.shape[2], x.dtype, x.device)
-            y = ops.processor_ep_fwd(x, wq, wk, wv, wo, bo, attn.heads, ep=ep, mode=mode, fused=fused, coef=coef,
-                                     begin=begin, end=0 if replay else end, n_plain=proc.plain_tail, ln=ln, residual=add_to,
-                                     ln_folded=ln_folded,
-                                     seg_executed=ops.executed_segments(mode, fused, vals, x.shape[0], None, begin, end),
-                                     attn_bias=bias, lora=lora.args(attn, x.dtype, x.device, False))
+            fused = proc.is_fused if mode != "plain" else False
+            layer = proc.endpoint_layer or f"layer@{id(attn):x}"
+            kw = dict(mode=mode, fused=fused, coef=coef, begin=begin, end=0 if replay else end,
+                      n_plain=proc.plain_tail if mode != "plain" else 0, ln=ln, residual=add_to, ln_folded=ln_folded,
+                      seg_executed=ops.executed_segments(mode, fused, vals, x.shape[0], None, begin, end),
+                      attn_bias=bias, lora=lora.args(attn, x.dtype, x.device, False))
+            if kstore is not None:
+                y = ops.processor_kf_fwd(x, wq, wk, wv, wo, bo, attn.heads,
+                                         kf=store.kf_args(layer, x.shape[1], x.shape[2], x.dtype, x.device), **kw)
+            else:
+                y = ops.processor_ep_fwd(x, wq, wk, wv, wo, bo, attn.heads,
+                                         ep=store.ep_args(layer, x.shape[1], x.shape[2], x.dtype, x.device), **kw)
             return _epilogue(attn, y, residual, shape4)
     if (exchange is not None or replay) and mode != "plain":
         # (a store's replay is one processor_fwd call below: LoRA, masks and the fused sublayer ride along)
@@ -896,6 +918,9 @@ class _IPBase(InterpolatedAttnProcessor):
                                "(interpolation.py:141-143, 352-359) — the reference fails at that broadcast; pass no mask")
         if getattr(self, "endpoint_store", None) is not None:
             raise NotImplementedError("an end-point store on an IP-Adapter processor: the image branch attends to the end points' image "
+                                      "keys, which the store does not hold (text processors only)")
+        if getattr(self, "keyframe_store", None) is not None:
+            raise NotImplementedError("a key-frame store on an IP-Adapter processor: the image branch attends to the end points' image "
                                       "keys, which the store does not hold (text processors only)")
         n = self._frames(x)
         wq, wk, wv, wo, bo = _weights(attn)

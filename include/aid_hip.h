@@ -526,6 +526,80 @@ size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args /* host */,
 int    aid_processor_ep_fwd(const AidProcessorArgs* args /* host */, const AidEndpointStore* ep /* host */, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Key-frame K / V^T store (no ABI version change: three new entry points, no existing struct changes).  An end point's trajectory
+ * depends on neither its partner nor the AID mode nor the fusion flag — it is plain attention of that frame — so ONE recording per
+ * KEY FRAME serves every pair that contains the frame, in both directions, and every early mode.  A key-frame store of one layer holds
+ * one frame, half of the pair slot above; every key frame has its own allocation:
+ *   k_store  [n_steps, k_fs]    vt_store [n_steps, vt_fs]      (element type of the call)
+ * aid_keyframe_rows moves, in ONE streaming launch, n_rows (1 .. AID_KF_MAX_ROWS) rows between a call's k / vt tensors and as many
+ * stores (`rows` is a HOST array; its entries travel by value in the kernel arguments).  For entry i:
+ *   AID_KF_PUT  reads  k[row_i * k_fs .. + k_fs), vt[row_i * vt_fs .. + vt_fs) and *step;
+ *               writes k_store_i[*step * k_fs .. + k_fs), vt_store_i[*step * vt_fs .. + vt_fs)
+ *   AID_KF_GET  reads what PUT writes (and *step), writes what PUT reads.  Nothing else is read or written.
+ * The whole block moves — gap rows and V^T pad columns included, exactly as aid_endpoint_rows moves them.  `step` is a DEVICE pointer
+ * read by the kernel: a launch captured into a graph addresses another slot at every replay with no node update.  A *step outside
+ * [0, n_steps) moves nothing (a memory-safety guard, not a mode: the host keeps the index in range).
+ * Requirements as aid_endpoint_rows: k_fs / vt_fs positive multiples of 8, k / vt and every k_store / vt_store 16-byte aligned
+ * (AID_ERR_SHAPE); f16 / bf16 / f32 (AID_ERR_DTYPE); NULL pointers (rows and every store included), step not 4-byte aligned, n_rows
+ * outside 1 .. AID_KF_MAX_ROWS, a negative row, n_steps < 1, a direction other than PUT / GET (AID_ERR_ARG) — all before any launch.
+ * 16-byte vector loads and stores on a grid-stride walk; no atomics, no LDS.
+ * ------------------------------------------------------------------------------------- */
+#define AID_KF_MAX_ROWS 8
+#define AID_KF_PUT 0          /* call  -> store */
+#define AID_KF_GET 1          /* store -> call  */
+
+typedef struct AidKeyframeRow {
+    void*   k_store;             /* [n_steps, k_fs]   of ONE key frame                         */
+    void*   vt_store;            /* [n_steps, vt_fs]                                           */
+    int32_t row;                 /* row of the call's k / vt                                   */
+} AidKeyframeRow;
+
+typedef struct AidKeyframeRows {
+    void*                 k;     /* [rows, k_fs]  of the call                                  */
+    void*                 vt;    /* [rows, vt_fs] of the call                                  */
+    const AidKeyframeRow* rows;  /* HOST: n_rows entries                                       */
+    const int32_t*        step;  /* DEVICE: the slot index, read by the kernel                 */
+    int64_t k_fs, vt_fs;         /* block sizes = row strides, in elements                     */
+    int32_t n_rows;              /* 1 .. AID_KF_MAX_ROWS                                       */
+    int32_t n_steps;
+    int32_t direction;           /* AID_KF_PUT / AID_KF_GET                                    */
+    int32_t dtype;               /* AID_DTYPE_*                                                */
+} AidKeyframeRows;
+
+int aid_keyframe_rows(const AidKeyframeRows* args /* host */, void* stream);
+
+/* aid_processor_fwd with key-frame stores of its layer beside it (AidProcessorArgs is unchanged).  kf == NULL is aid_processor_fwd.
+ *   AID_KF_RECORD  `args` is a PLAIN self-attention call (ctx == NULL, ip == NULL, mode == AID_MODE_PLAIN) over a batch that holds the
+ *                  key frames; `rows` has 1 .. AID_KF_MAX_ROWS entries with distinct rows < n_frames.  Exactly aid_processor_fwd(args)
+ *                  plus one AID_KF_PUT of those rows of the call's k / V^T behind the projection launch: y is bit-identical,
+ *                  aid_processor_kf_workspace_bytes == aid_processor_workspace_bytes.
+ *   AID_KF_REPLAY  `rows` has exactly TWO entries: entry 0 the begin frame's store, entry 1 the end frame's (`row` is ignored).
+ *                  `args` describes the LOCAL frames only, with an AID mode, as in AID_EP_REPLAY: the workspace gives k / V^T two rows
+ *                  more than n_frames, one AID_KF_GET fills rows n_frames (begin) and n_frames + 1 (end) from the two stores, and the
+ *                  rest of the call runs unchanged with begin = n_frames, end = n_frames + 1 (args->begin / args->end are not
+ *                  read).  It IS the AID_EP_REPLAY path — only the copy launch that fills the two rows differs — and
+ *                  aid_processor_kf_workspace_bytes equals aid_processor_ep_workspace_bytes of a replay.  Swapping the two entries
+ *                  renders the reverse direction.
+ * The stores' blocks are k_fs = s * c and vt_fs = c * round_up(s, 8) elements of args->dtype.  ctx != NULL, ip != NULL, RECORD on an
+ * AID call, REPLAY on a PLAIN call, REPLAY with n_rows != 2, a duplicate or out-of-range row in RECORD, NULL rows / store / step
+ * pointers, n_steps < 1 or a mode other than RECORD / REPLAY is AID_ERR_ARG, a misaligned store AID_ERR_SHAPE — checked, with
+ * everything aid_processor_fwd checks, before the first launch.  LoRA / DoRA, attn_bias, LayerNorm (folded or not), residual,
+ * f32_split / f32_attn_split work as in aid_processor_fwd: it is the same code path. */
+#define AID_KF_RECORD 1
+#define AID_KF_REPLAY 2
+
+typedef struct AidKeyframeCall {
+    const AidKeyframeRow* rows;  /* HOST: n_rows entries (RECORD: 1 .. AID_KF_MAX_ROWS; REPLAY: 2) */
+    const int32_t*        step;  /* DEVICE: the AID step of this call                          */
+    int32_t n_rows;
+    int32_t n_steps;
+    int32_t mode;                /* AID_KF_RECORD / AID_KF_REPLAY                              */
+} AidKeyframeCall;
+
+size_t aid_processor_kf_workspace_bytes(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */);
+int    aid_processor_kf_fwd(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
