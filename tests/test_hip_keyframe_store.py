@@ -286,6 +286,78 @@ def test_replay_with_cfg_riders(mode, fused):
     _close(y, ref, F16, "replay of frames 1..3 + 2 PLAIN riders")
 
 
+# ---- the library call at shapes that reach the production engines ---------------------------------------------------------------------
+# SHAPES above stay at S <= 40 (resident, text-key, one tile of the streaming kernel).  These reach the ping-pong kernel by the default
+# rule (S = 1024, d = 64: the path of the SDXL self-attention layers) and alone under ATTN_V2 = 1, the streaming program-order kernel
+# with several key tiles and query blocks (d = 40, d = 160) and the fp32 kernel.  (s, c, heads, dtype, mode, fused, knobs, variant)
+def _engine_cases():
+    out = []
+    for dt in (BF16, F16):
+        for mode in ("outer", "inner"):
+            out.append((1024, 64, 1, dt, mode, True, {}, f"aid_attn_pp<d64,{mode}>"))
+    for mode in ("outer", "inner"):
+        out.append((512, 128, 2, BF16, mode, False, {"ATTN_V2": 1}, f"aid_attn_pp<d64,{mode}>"))
+    for dt in (F16, F32):
+        for mode, fused in MODES:
+            out.append((200, 80, 2, dt, mode, fused, {}, "aid_attn_f32" if dt == F32 else "d40"))
+    out.append((136, 160, 1, BF16, "outer", True, {}, "d160"))
+    ids = {F16: "f16", BF16: "bf16", F32: "f32"}
+    return [pytest.param(*c, id=f"s{c[0]}-c{c[1]}-{ids[c[3]]}-{'fused' if c[5] else 'pure'}_{c[4]}") for c in out]
+
+
+def _assert_variant(variant, what):
+    name = ops.last_attn_variant()
+    if variant.startswith("aid_attn_"):
+        assert name == variant, (what, name)
+    else:
+        assert name.startswith("aid_attn<") and f",{variant}," in name, (what, name)
+
+
+def _poison_workspace(byte):
+    """Fill the library workspace of the current stream (one buffer reused by every call) with ``byte``."""
+    ops.workspace(1, torch.device(DEV)).fill_(byte)
+
+
+@pytest.mark.parametrize("s,c,heads,dtype,mode,fused,knobs,variant", _engine_cases())
+def test_replay_on_the_production_engines(s, c, heads, dtype, mode, fused, knobs, variant, tuning):
+    """Replay frames 1..3 and frame 2 alone from the two key frames' stores against the fp64 oracle of the full batch, the engine
+    asserted by name after each replay call; the S = 1024 shape also in the (B, A) direction.  (Nothing is compared bit for bit
+    across record and replay: the smaller m takes another GEMM tile plan.)"""
+    for name, value in knobs.items():
+        tuning(name, value)
+    L = _layer(s, c, heads, dtype)
+    ref = L.ref(mode, fused)
+    y = L.replay(mode, fused)
+    _assert_variant(variant, "frames 1..3")
+    _close(y, ref[1:4], dtype, "replay (A, B) of frames 1..3")
+    y = L.replay(mode, fused, rows=slice(2, 3))
+    _assert_variant(variant, "frame 2 alone")
+    _close(y, ref[2:3], dtype, "replay (A, B) of frame 2 alone")
+    if s == 1024:
+        y = L.replay(mode, fused, reverse=True)
+        _assert_variant(variant, "(B, A)")
+        _close(y, L.ref(mode, fused, reverse=True)[1:4], dtype, "replay (B, A) of frames 1..3")
+
+
+@pytest.mark.parametrize("mode", ["outer", "inner"])
+@pytest.mark.parametrize("s", [75, 512], ids=lambda s: f"s{s}")
+def test_replay_does_not_depend_on_stale_workspace(s, mode):
+    """The two stored rows live in the workspace behind the projected ones (S = 75: V^T rows with pad columns).  After a larger call
+    has left its data there, the same replay on a workspace of 0xFF bytes (NaN) and on one of zeros gives equal, finite bits (as
+    test_hip_memory_contracts.py::test_processor_output_does_not_depend_on_stale_workspace)."""
+    c, heads, dtype = 128, 2, BF16
+    L = _layer(s, c, heads, dtype)
+    big = torch.randn(N, 2 * s + 256, c, device=DEV).to(dtype)
+    outs = []
+    for byte in (0xFF, 0x00):
+        ops.processor_fwd(big, None, *L.w, L.bo, heads, mode=mode, fused=True, coef=L.coef.to(DEV), begin=0, end=N - 1)
+        _poison_workspace(byte)
+        outs.append(L.replay(mode, True, riders=1).clone())
+    assert torch.equal(_bits(outs[0]), _bits(outs[1])), "the replay depends on the workspace contents"
+    ref = np.concatenate([L.ref(mode, True)[1:4], O.plain_attention(to_np64(L.riders[:1]), None, L.w64)])
+    _close(outs[0], ref, dtype, "replay on a poisoned workspace")
+
+
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
 def test_replay_with_a_lora_segment(dtype):
     """Unmerged LoRA adapters on q / k / v, in the recording calls and in the replay: the same code path; the oracle computes with

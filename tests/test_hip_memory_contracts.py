@@ -17,6 +17,7 @@ import torch
 
 from guarded import Guarded, round_up
 from oracle import aid_oracle as O
+from replay_rows import attn_ref as _attn_ref
 from util import TOL, TOL_GEMM, WORST, rel_l2, to_np64, worst
 
 pytestmark = pytest.mark.gpu
@@ -274,58 +275,20 @@ def test_gemm_f32_memory_contract(kw, tuning):
 # ================================================================================================================================
 # attention core, aid_lerp_kv
 # ================================================================================================================================
-def _sdpa(q, k, v, h, scale, bias=None):
-    """fp64 softmax(q k^T * scale + bias) v per head; q [s, c], k / v [L, c], bias [s, L] or None."""
-    s, c = q.shape
-    d = c // h
-    qh, kh, vh = (t.reshape(t.shape[0], h, d).transpose(1, 0, 2) for t in (q, k, v))
-    sc = qh @ kh.transpose(0, 2, 1) * scale
-    if bias is not None:
-        sc = sc + bias[None]
-    sc = sc - sc.max(axis=-1, keepdims=True)
-    p = np.exp(sc)
-    p /= p.sum(axis=-1, keepdims=True)
-    return (p @ vh).transpose(1, 0, 2).reshape(s, c)
-
-
-def _attn_ref(q, k, v, h, mode, fused, coef, begin, end, kv_map=None, bias=None):
-    """fp64 AID attention (aid_hip.h AidAttnArgs), frame by frame: riders (negative coefficient) attend PLAIN to their own keys."""
-    n, _, c = q.shape
-    scale = (c // h) ** -0.5
-    out = []
-    for i in range(n):
-        own = i if kv_map is None else int(kv_map[i])
-        b_ = None if bias is None else bias[i]
-        ci = None if coef is None else float(coef[i])
-        if mode == "plain" or ci < 0:
-            out.append(_sdpa(q[i], k[own], v[own], h, scale, b_))
-            continue
-        if mode == "inner":
-            kc, vc = (1 - ci) * k[begin] + ci * k[end], (1 - ci) * v[begin] + ci * v[end]
-            if fused:
-                kc, vc = np.concatenate([k[own], kc]), np.concatenate([v[own], vc])
-            out.append(_sdpa(q[i], kc, vc, h, scale, b_))
-        else:
-            sides = []
-            for e in (begin, end):
-                ke, ve = (np.concatenate([k[own], k[e]]), np.concatenate([v[own], v[e]])) if fused else (k[e], v[e])
-                sides.append(_sdpa(q[i], ke, ve, h, scale, b_))
-            out.append((1 - ci) * sides[0] + ci * sides[1])
-    return np.stack(out)
-
-
 class AttnCall:
     """q / k / V^T / out of one aid_attn_fwd call on guarded buffers: ldq, ldk > c, ldvt = round_up(l, 8) + 8 with NaN pad columns,
-    a gap row behind every frame, out with row stride ``ldo`` and the sentinel outside [s, c] of every frame."""
+    a gap row behind every frame, out with row stride ``ldo`` and the sentinel outside [s, c] of every frame.  ``extra_kv``: K / V^T
+    hold that many frames more than q (n_kv = n + extra_kv: the replay layout, end-point rows behind the call's own)."""
 
-    def __init__(self, dtype, n, s, l, h, d, ldo_extra, seed, fill="nan"):
+    def __init__(self, dtype, n, s, l, h, d, ldo_extra, seed, fill="nan", extra_kv=0):
         self.dtype, self.n, self.s, self.l, self.h, self.d = dtype, n, s, l, h, d
+        f = self.n_kv = n + extra_kv
         c = self.c = h * d
         g = torch.Generator().manual_seed(seed)
         self.Q = Guarded(n, s, c, dtype, DEV, ld=c + 8, gap_rows=1, fill=fill).set(torch.randn(n, s, c, generator=g))
-        self.K = Guarded(n, l, c, dtype, DEV, ld=c + 16, gap_rows=1, fill=fill).set(torch.randn(n, l, c, generator=g))
-        v = torch.randn(n, l, c, generator=g)
-        self.VT = Guarded(n, c, l, dtype, DEV, ld=round_up(l, 8) + 8, gap_rows=1, fill=fill).set(v.transpose(1, 2))
+        self.K = Guarded(f, l, c, dtype, DEV, ld=c + 16, gap_rows=1, fill=fill).set(torch.randn(f, l, c, generator=g))
+        v = torch.randn(f, l, c, generator=g)
+        self.VT = Guarded(f, c, l, dtype, DEV, ld=round_up(l, 8) + 8, gap_rows=1, fill=fill).set(v.transpose(1, 2))
         self.ldo = c + ldo_extra
         self.q64, self.k64 = to_np64(self.Q.view), to_np64(self.K.view)
         self.v64 = to_np64(self.VT.view).transpose(0, 2, 1)
@@ -357,7 +320,7 @@ class AttnCall:
             base=None, bias=None, k2=None, vt2=None):
         """One aid_attn_fwd through the C ABI; returns (variant, out Guarded, fp64 expected [n, s, c])."""
         n, s, c, l = self.n, self.s, self.c, self.l
-        end = end % n
+        end = end % self.n_kv
         Og = self.out_buffer()
         if accumulate:
             Og.view.copy_(base)
@@ -370,7 +333,7 @@ class AttnCall:
         a.kv_map = None if map_t is None else map_t.data_ptr()
         if k2 is not None:
             a.k2, a.vt2 = k2.ptr, vt2.ptr
-        a.n_frames, a.n_kv, a.s, a.l, a.heads, a.d = n, n, s, l, self.h, self.d
+        a.n_frames, a.n_kv, a.s, a.l, a.heads, a.d = n, self.n_kv, s, l, self.h, self.d
         a.ldq, a.ldk, a.ldvt, a.ldo = self.Q.ld, self.K.ld, self.VT.ld, self.ldo
         a.q_fs, a.k_fs, a.vt_fs, a.o_fs = self.Q.fs, self.K.fs, self.VT.fs, Og.fs
         a.mode, a.fused, a.begin, a.end = ops.MODES[mode], int(fused), begin, end
@@ -466,6 +429,28 @@ def test_attention_variant_memory_contract(variant, dtype, s, tuning):
             assert ("bias" in name) or dtype == torch.float32, name
             call.check(name, Og, ref, ("bias", mode))
             _ok(bias.inputs_unchanged())
+
+
+@pytest.mark.parametrize("s", [1, 67], ids=lambda s: f"s{s}")
+@pytest.mark.parametrize("variant,dtype", ATTN_PARAMS)
+def test_attention_variant_replay_rows_memory_contract(variant, dtype, s, tuning):
+    """The replay layout of the end-point / key-frame stores on guarded buffers: K / V^T hold two rows more than q (n_kv = n + 2),
+    begin = n, end = n + 1, no frame of the batch is an end point; frame 2 has a coefficient of exactly 1 with own keys that are not
+    the end row (one-sided), frame 3 rides PLAIN.  aid_lerp_kv writes into guarded k2 / vt2 of n frames: an interpolated row written
+    at ``begin`` / ``end`` would land in the guard band, only frames 0 and 1 may be written.  Then the four AID modes: fp64 parity, a
+    finite result, the sentinel untouched outside [s, c] of every frame, the inputs unchanged."""
+    vid, _, d, l, knobs, ldo_extra, family, _ = variant
+    for k_, v_ in knobs.items():
+        tuning(k_, v_)
+    n, h = 4, 2
+    call = AttnCall(dtype, n, s, l, h, d, ldo_extra, seed=d * 100 + l + s + 1, extra_kv=2)
+    coef = [0.25, 0.75, 1.0, -1.0]
+    k2, vt2 = call.lerp(torch.tensor(coef, dtype=torch.float32, device=DEV), n, n + 1)
+    for mode, fused in ATTN_MODES[1:]:
+        kw = dict(k2=k2, vt2=vt2) if mode == "inner" else {}
+        name, Og, ref = call.run(mode, fused, coef, n, n + 1, **kw)
+        assert name.startswith(family), (vid, mode, fused, name)
+        call.check(name, Og, ref, ("replay", mode, fused))
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids_dt)
