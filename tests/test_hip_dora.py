@@ -53,12 +53,12 @@ def _gemm_tol(dtype):
 N_OUT, N_IN, LDW = 200, 328, 336
 
 
-def _gain_inputs(dtype, rank, seed):
+def _gain_inputs(dtype, rank, seed, n_out=N_OUT, n_in=N_IN):
     g = torch.Generator().manual_seed(seed)
-    w = torch.randn(N_OUT, N_IN, generator=g).to(dtype)
-    a = (torch.randn(rank, N_IN, generator=g) / N_IN ** 0.5).to(dtype)
-    b = (torch.randn(N_OUT, rank, generator=g) / rank ** 0.5).to(dtype)
-    mag = (torch.linalg.norm(w.float(), dim=1) * (0.5 + torch.rand(N_OUT, generator=g))).to(dtype)
+    w = torch.randn(n_out, n_in, generator=g).to(dtype)
+    a = (torch.randn(rank, n_in, generator=g) / n_in ** 0.5).to(dtype)
+    b = (torch.randn(n_out, rank, generator=g) / rank ** 0.5).to(dtype)
+    mag = (torch.linalg.norm(w.float(), dim=1) * (0.5 + torch.rand(n_out, generator=g))).to(dtype)
     t = w.double() + b.double() @ a.double()
     want = (mag.double() / torch.linalg.norm(t, dim=1)).numpy()
     return w, a, b, mag, want
@@ -99,6 +99,33 @@ def test_dora_gain_memory_contract(dtype, rank):
     assert G.untouched(G.layout.region_mask()) == ""
     for gd in (W, A, B, M):
         assert gd.inputs_unchanged() == ""
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rank", [64, 512])
+@pytest.mark.parametrize("n_out", [1, 3, 203])
+@pytest.mark.parametrize("n_in", [8, 1280, 2048, 4096])
+def test_dora_gain_rank_rows_and_widths(dtype, rank, n_out, n_in):
+    """The edges of the kernel's three loops: the maximum rank 512 next to 64; n_out below DORA_ROWS = 4 and not a multiple of it (the
+    last workgroup clamps its rows and drops their results); n_in of one 16-byte chunk (one wave, 63 idle lanes for 16-bit storage), of
+    3 and 4 waves (1280 / 8 = 160, 2048 / 8 = 256 chunks) and of two chunks per lane (4096), rows of w 8 elements apart from the next
+    (NaN in the pad).  The output is a NaN-prefilled buffer of n_out + 4 floats: exactly n_out are written.  Bound: TOL_GEMM32."""
+    w, a, b, mag, want = _gain_inputs(dtype, rank, 7 * rank + n_out + n_in, n_out, n_in)
+    ldw = n_in + 8
+    wbuf = torch.full((n_out, ldw), float("nan"), dtype=dtype, device=DEV)
+    wbuf[:, :n_in] = w.to(DEV)
+    a, b, mag = a.to(DEV), b.to(DEV), mag.to(DEV)
+    out = torch.full((n_out + 4,), float("nan"), dtype=torch.float32, device=DEV)
+    rc = _lib.load().aid_dora_gain(wbuf.data_ptr(), a.data_ptr(), b.data_ptr(), mag.data_ptr(), out.data_ptr(), n_out, n_in, ldw, rank,
+                                   ops._dtype_code(wbuf), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0
+    torch.cuda.synchronize()
+    got = to_np64(out[:n_out])
+    assert np.isfinite(got).all()
+    err = rel_l2(got, want)
+    print(f"dora_gain {dtype} rank {rank} n_out {n_out} n_in {n_in}: rel-L2 {err:.3e}")
+    assert err <= TOL_GEMM32
+    assert bool(torch.isnan(out[n_out:]).all()), "written behind n_out"
 
 
 # ---- GEMM with a row gain ---------------------------------------------------------------------------------------------------------------
