@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
     "aid_endpoint_rows", "aid_processor_ep_workspace_bytes", "aid_processor_ep_fwd",
     "aid_keyframe_rows", "aid_processor_kf_workspace_bytes", "aid_processor_kf_fwd",
+    "aid_q8_block_bytes", "aid_keyframe_rows_q8", "aid_processor_kf_q8_workspace_bytes", "aid_processor_kf_q8_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -144,6 +145,14 @@ class AidKeyframeRows(C.Structure):
     ]
 
 
+class AidKeyframeRowsQ8(C.Structure):
+    _fields_ = [
+        ("k", C.c_void_p), ("vt", C.c_void_p), ("rows", C.POINTER(AidKeyframeRow)), ("step", C.c_void_p),
+        ("k_fs", C.c_int64), ("vt_fs", C.c_int64), ("vt_ld", C.c_int32), ("vt_cols", C.c_int32),
+        ("n_rows", C.c_int32), ("n_steps", C.c_int32), ("direction", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 class AidKeyframeCall(C.Structure):
     _fields_ = [
         ("rows", C.POINTER(AidKeyframeRow)), ("step", C.c_void_p),
@@ -233,6 +242,14 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_kf_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall)]
     lib.aid_processor_kf_fwd.restype = C.c_int
     lib.aid_processor_kf_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall), C.c_void_p]
+    lib.aid_q8_block_bytes.restype = C.c_size_t
+    lib.aid_q8_block_bytes.argtypes = [C.c_int64]
+    lib.aid_keyframe_rows_q8.restype = C.c_int
+    lib.aid_keyframe_rows_q8.argtypes = [C.POINTER(AidKeyframeRowsQ8), C.c_void_p]
+    lib.aid_processor_kf_q8_workspace_bytes.restype = C.c_size_t
+    lib.aid_processor_kf_q8_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall)]
+    lib.aid_processor_kf_q8_fwd.restype = C.c_int
+    lib.aid_processor_kf_q8_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall), C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

@@ -658,6 +658,38 @@ int aid_keyframe_rows(const AidKeyframeRows* args, void* stream) {
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_keyframe_rows");
 }
 
+size_t aid_q8_block_bytes(int64_t n_elements) {
+    if (n_elements < 8 || n_elements % 8) return 0;
+    return (size_t)((n_elements + (n_elements + 31) / 32 + 15) / 16 * 16);
+}
+
+int aid_keyframe_rows_q8(const AidKeyframeRowsQ8* args, void* stream) {
+    if (!args) return AID_ERR_ARG;
+    const AidKeyframeRowsQ8& a = *args;
+    if (!a.k || !a.vt || !a.rows || !a.step || !aligned4(a.step)) return AID_ERR_ARG;
+    if (a.n_rows < 1 || a.n_rows > AID_KF_MAX_ROWS || a.n_steps < 1) return AID_ERR_ARG;
+    for (int i = 0; i < a.n_rows; ++i)
+        if (!a.rows[i].k_store || !a.rows[i].vt_store || a.rows[i].row < 0) return AID_ERR_ARG;
+    if (a.direction != AID_KF_PUT && a.direction != AID_KF_GET) return AID_ERR_ARG;
+    if (!dtype_ok(a.dtype)) return AID_ERR_DTYPE;
+    if (a.k_fs < 8 || a.vt_fs < 8 || a.k_fs % 8 || a.vt_fs % 8) return AID_ERR_SHAPE;
+    if (a.vt_ld < 8 || a.vt_ld % 8 || a.vt_fs % a.vt_ld || a.vt_cols < 1 || a.vt_cols > a.vt_ld) return AID_ERR_SHAPE;
+    if (!aligned16(a.k) || !aligned16(a.vt)) return AID_ERR_SHAPE;
+    for (int i = 0; i < a.n_rows; ++i)
+        if (!aligned16(a.rows[i].k_store) || !aligned16(a.rows[i].vt_store)) return AID_ERR_SHAPE;
+    hipError_t e;
+    {
+        // traffic: the two blocks of every entry on the call side, their int8 and exponent bytes on the store side
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_keyframe_rows_q8<%s,%s>", dtype_name(a.dtype), a.direction == AID_KF_PUT ? "put" : "get");
+        const double stored = (double)(a.k_fs + (a.k_fs + 31) / 32 + a.vt_fs + (a.vt_fs + 31) / 32);
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 0.0,
+                     a.n_rows * ((a.dtype == AID_DTYPE_F32 ? 4.0 : 2.0) * (double)(a.k_fs + a.vt_fs) + stored));
+        e = aid::keyframe_rows_q8_launch(a, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_keyframe_rows_q8");
+}
+
 // end-point store beside a processor call (aid_hip.h): self-attention AID calls only
 static int check_endpoint_store(const AidProcessorArgs& a, const AidEndpointStore& ep) {
     if (ep.mode != AID_EP_RECORD && ep.mode != AID_EP_REPLAY) return AID_ERR_ARG;
@@ -688,7 +720,7 @@ static int check_keyframe_call(const AidProcessorArgs& a, const AidKeyframeCall&
 }
 
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream);
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8 = false);
 
 size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidEndpointStore* ep) {
     if (!args) return 0;
@@ -722,10 +754,20 @@ int aid_processor_kf_fwd(const AidProcessorArgs* args, const AidKeyframeCall* kf
     return processor_impl(args, nullptr, 0, nullptr, kf, stream);
 }
 
-// ``ep`` / ``kf`` (at most one of them): which copy launch stands behind the projections — a pair store's aid_endpoint_rows or the
-// key-frame stores' aid_keyframe_rows.  Both replays are the same call: two rows more of k / V^T, filled by that launch.
+// the q8 stores change the copy launch alone: the checks and the workspace are aid_processor_kf_fwd's
+size_t aid_processor_kf_q8_workspace_bytes(const AidProcessorArgs* args, const AidKeyframeCall* kf) {
+    return aid_processor_kf_workspace_bytes(args, kf);
+}
+
+int aid_processor_kf_q8_fwd(const AidProcessorArgs* args, const AidKeyframeCall* kf, void* stream) {
+    return processor_impl(args, nullptr, 0, nullptr, kf, stream, true);
+}
+
+// ``ep`` / ``kf`` (at most one of them): which copy launch stands behind the projections — a pair store's aid_endpoint_rows, the
+// key-frame stores' aid_keyframe_rows or, with ``kf_q8``, aid_keyframe_rows_q8 on 8-bit block stores.  All replays are the same call:
+// two rows more of k / V^T, filled by that launch.
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream) {
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8) {
     if (!args) return AID_ERR_ARG;
     AidProcessorArgs a_local;
     const bool replay = (ep && ep->mode == AID_EP_REPLAY) || (kf && kf->mode == AID_KF_REPLAY);
@@ -920,7 +962,16 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         kr.k_fs = (int64_t)l * a.c; kr.vt_fs = (int64_t)a.c * cv.lp;
         kr.direction = replay ? AID_KF_GET : AID_KF_PUT;
         kr.dtype = a.dtype;
-        rc = aid_keyframe_rows(&kr, stream);
+        if (kf_q8) {                                          // the same rows, (de)quantised in the lane; the keys are the stored columns
+            AidKeyframeRowsQ8 kq;
+            memset(&kq, 0, sizeof(kq));
+            kq.k = kr.k; kq.vt = kr.vt; kq.rows = kr.rows; kq.step = kr.step;
+            kq.k_fs = kr.k_fs; kq.vt_fs = kr.vt_fs; kq.vt_ld = cv.lp; kq.vt_cols = l;
+            kq.n_rows = kr.n_rows; kq.n_steps = kr.n_steps; kq.direction = kr.direction; kq.dtype = kr.dtype;
+            rc = aid_keyframe_rows_q8(&kq, stream);
+        } else {
+            rc = aid_keyframe_rows(&kr, stream);
+        }
         if (rc != AID_OK) return rc;
     }
 

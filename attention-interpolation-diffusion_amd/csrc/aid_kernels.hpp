@@ -205,6 +205,9 @@ hipError_t endpoint_rows_launch(const AidEndpointRows& a, hipStream_t stream);
 // key-frame K / V^T rows between a call and slot *step of up to AID_KF_MAX_ROWS key-frame stores (aid_keyframe.hip); arguments checked
 // by the caller
 hipError_t keyframe_rows_launch(const AidKeyframeRows& a, hipStream_t stream);
+// the same rows between a call and 8-bit block stores, quantised on PUT and dequantised on GET (aid_keyframe_q8.hip); arguments
+// checked by the caller
+hipError_t keyframe_rows_q8_launch(const AidKeyframeRowsQ8& a, hipStream_t stream);
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,
                             int dtype, hipStream_t stream);
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);

@@ -15,6 +15,16 @@ replay under anything else raises.
 
 ``pipe.record_keyframes(store, names, ...)`` records; ``pipe.interpolate_between(store, a, b)`` / ``pipe.interpolate_chain(store,
 [a, b, c])`` replay: only the interior frames go through the UNet.
+
+``KeyframeStore(storage="q8")`` keeps the K / V^T blocks in an 8-bit block format instead of the storage dtype (DESIGN.md §3.6e,
+include/aid_hip.h): 32 int8 elements share one power-of-two exponent byte — 8.25 bits per element, 0.516x of a 16-bit store and
+0.258x of a float32 one.  It is LOSSY and OPT-IN: the recording launch quantises, the replaying one dequantises, and every stored
+element comes back within ``|y - x| <= 2^(e-1) < a / 127`` of what was recorded, ``a`` the largest magnitude of its block of 32
+(relative L2 about 8e-3 on normal data).  The recording run itself is not touched — its frames and final latents are bit for bit a
+native store's — and neither is anything behind the dequantising launch; only the interior frames a replay renders move, by what
+DESIGN.md §3.6e measures against the fp64 loop.  Latents, embeddings and final latents stay unquantised.  Use it when the stores do
+not fit otherwise (twelve SDXL key frames: 126 GB native, 65 GB q8); keep ``"native"`` (the default, unchanged) where a replay must
+reproduce the full run to the storage dtype's own precision.
 """
 from __future__ import annotations
 
@@ -52,11 +62,15 @@ class Keyframe:
 class KeyframeStore(StepIndex):
     """See the module docstring.  ``max_bytes``: a recording that would need more raises ``ValueError`` naming the bytes needed, before
     the buffer that crosses the limit is allocated — and what the refused recording had allocated so far is dropped; the frames
-    recorded earlier stay."""
+    recorded earlier stay.  ``storage``: "native" (the K / V^T blocks verbatim, in the storage dtype) or "q8" (8-bit blocks: lossy, about
+    half the bytes of a 16-bit store — see the module docstring); a store has one storage for its life."""
 
-    def __init__(self, max_bytes: Optional[int] = None):
+    def __init__(self, max_bytes: Optional[int] = None, storage: str = "native"):
         if max_bytes is not None and int(max_bytes) < 0:
             raise ValueError("max_bytes must be None or >= 0")
+        if storage not in ops.KF_STORAGES:
+            raise ValueError(f"storage must be 'native' or 'q8'; got {storage!r}")
+        self._storage = storage
         self.max_bytes = None if max_bytes is None else int(max_bytes)
         self._step: Optional[torch.Tensor] = None
         self.clear()
@@ -71,6 +85,11 @@ class KeyframeStore(StepIndex):
         self._pending: Dict[str, Keyframe] = {}    # the frames of the recording in progress, in batch order
         self._pair: Optional[Tuple[str, str]] = None
         self.step = -1
+
+    @property
+    def storage(self) -> str:
+        """"native" or "q8": how the K / V^T blocks are kept (fixed at construction)."""
+        return self._storage
 
     @property
     def names(self) -> List[str]:
@@ -104,10 +123,15 @@ class KeyframeStore(StepIndex):
         return self[name].nbytes
 
     @staticmethod
-    def layer_bytes(n_steps: int, l: int, c: int, dtype: torch.dtype) -> int:
+    def layer_bytes(n_steps: int, l: int, c: int, dtype: torch.dtype, storage: str = "native") -> int:
         """Bytes of one self-attention layer of ONE key frame with ``l`` tokens of width ``c``: n_steps * (l c + c round_up(l, 8))
-        elements — half of ``EndpointStore.layer_bytes``."""
+        elements — half of ``EndpointStore.layer_bytes``.  ``storage="q8"``: n_steps * (q8_block_bytes(l c) + q8_block_bytes(c
+        round_up(l, 8))) bytes, whatever the dtype."""
         k_fs, vt_fs = ops.endpoint_block_sizes(l, c)
+        if storage == "q8":
+            return n_steps * (ops.q8_block_bytes(k_fs) + ops.q8_block_bytes(vt_fs))
+        if storage != "native":
+            raise ValueError(f"storage must be 'native' or 'q8'; got {storage!r}")
         return n_steps * (k_fs + vt_fs) * (torch.finfo(dtype).bits // 8)
 
     # -- settings ---------------------------------------------------------------------------------------------------------------
@@ -191,35 +215,52 @@ class KeyframeStore(StepIndex):
         the recording as rows 0 .. K-1 of the batch (their buffers are allocated at the layer's first recorded call); REPLAY, the
         stores of the pair's begin and end frame."""
         k_fs, vt_fs = ops.endpoint_block_sizes(l, c)
+        q8 = self._storage == "q8"
         if self.mode == "record":
             entries = []
             for row, frame in enumerate(list(self._pending.values())):
                 hit = frame.layers.get(layer)
                 if hit is None:
-                    self._refuse_over(self.nbytes + self.layer_bytes(self.n_steps, l, c, dtype))
+                    self._refuse_over(self.nbytes + self.layer_bytes(self.n_steps, l, c, dtype, self._storage))
                     if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("the first recorded call of a layer allocates its stores: run the pass once eagerly before "
                                            "capturing")
-                    hit = (torch.empty(self.n_steps, k_fs, dtype=dtype, device=device),
+                    hit = (torch.empty(self.n_steps, ops.q8_block_bytes(k_fs), dtype=torch.uint8, device=device),
+                           torch.empty(self.n_steps, ops.q8_block_bytes(vt_fs), dtype=torch.uint8, device=device)) if q8 else \
+                          (torch.empty(self.n_steps, k_fs, dtype=dtype, device=device),
                            torch.empty(self.n_steps, vt_fs, dtype=dtype, device=device))
                     frame.layers[layer] = hit
-                self._check_block(layer, hit, k_fs, vt_fs, dtype, device)
+                self._check_block(layer, hit, k_fs, vt_fs, dtype, device, self._storage)
                 entries.append((hit[0], hit[1], row))
-            return dict(entries=entries, step=self._step, mode="record")
+            return self._kf(entries, "record")
         if self.mode == "replay":
             entries = []
             for name in self._pair:
                 hit = self.frames[name].layers.get(layer)
                 if hit is None:
                     raise RuntimeError(f"key frame {name!r} holds no rows of layer {layer!r}: it was recorded on another UNet")
-                self._check_block(layer, hit, k_fs, vt_fs, dtype, device)
+                self._check_block(layer, hit, k_fs, vt_fs, dtype, device, self._storage)
                 entries.append((hit[0], hit[1], 0))
-            return dict(entries=entries, step=self._step, mode="replay")
+            return self._kf(entries, "replay")
         raise RuntimeError("the key-frame store is attached to a processor outside a run (record_keyframes / interpolate_between)")
 
+    def _kf(self, entries, mode: str) -> dict:
+        """(a native store's dictionary is what it always was; a q8 store's names its storage)"""
+        kf = dict(entries=entries, step=self._step, mode=mode)
+        if self._storage != "native":
+            kf["storage"] = self._storage
+        return kf
+
     @staticmethod
-    def _check_block(layer, hit, k_fs, vt_fs, dtype, device) -> None:
+    def _check_block(layer, hit, k_fs, vt_fs, dtype, device, storage: str = "native") -> None:
         k_store, vt_store = hit
+        if storage == "q8":
+            kb, vb = ops.q8_block_bytes(k_fs), ops.q8_block_bytes(vt_fs)
+            if k_store.shape[1] != kb or vt_store.shape[1] != vb or k_store.dtype != torch.uint8 or k_store.device != torch.device(device):
+                raise ValueError(f"layer {layer!r}: the q8 store holds block rows of {k_store.shape[1]} / {vt_store.shape[1]} bytes "
+                                 f"({k_store.dtype}) on {k_store.device}, this call needs {kb} / {vb} bytes ({k_fs} / {vt_fs} elements) "
+                                 f"on {device} (another resolution or device)")
+            return
         if k_store.shape[1] != k_fs or vt_store.shape[1] != vt_fs or k_store.dtype != dtype or k_store.device != torch.device(device):
             raise ValueError(f"layer {layer!r}: the store holds blocks of {k_store.shape[1]} / {vt_store.shape[1]} {k_store.dtype} elements "
                              f"on {k_store.device}, this call needs {k_fs} / {vt_fs} {dtype} on {device} (another resolution, dtype or device)")

@@ -263,15 +263,22 @@ class AidDenoiseLoop:
         self._warmed = {(which, cache_generation())}
 
     @staticmethod
-    def _graph_key(which: str):
-        """A graph holds the kernels of the float32 matmul precision and of the attention core's precision it was captured under."""
+    def _graph_key(which: str, unet=None):
+        """A graph holds the kernels of the float32 matmul precision and of the attention core's precision it was captured under —
+        and, where a key-frame store with another storage than "native" is attached to ``unet`` (``set_keyframe_store``), that store's
+        copy launch: its storage joins the key."""
         from . import ops
-        return (which, ops.f32_split_code(), ops.f32_attn_split_code())
+        key = (which, ops.f32_split_code(), ops.f32_attn_split_code())
+        for proc in (getattr(unet, "attn_processors", None) or {}).values():
+            storage = getattr(getattr(proc, "keyframe_store", None), "storage", "native")
+            if storage != "native":
+                return key + (storage,)
+        return key
 
     def _run(self, which: str):
         if not self.use_graphs:
             return self._pass(which)
-        gk = self._graph_key(which)
+        gk = self._graph_key(which, self.unet)
         g = self._graphs.get(gk)
         if g is None:
             cur = torch.cuda.current_stream()

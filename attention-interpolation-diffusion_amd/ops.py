@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME,
                    KF_GET, KF_MAX_ROWS, KF_PUT, KF_RECORD, KF_REPLAY, MODE_INNER, MODE_OUTER, MODE_PLAIN,
                    AidAttnArgs, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeCall,
-                   AidKeyframeRow, AidKeyframeRows, AidProcessorArgs)
+                   AidKeyframeRow, AidKeyframeRows, AidKeyframeRowsQ8, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
 IP_MODES = {"same": IP_SAME, "plain": IP_PLAIN}
@@ -27,6 +27,7 @@ EP_MODES = {"record": EP_RECORD, "replay": EP_REPLAY}
 EP_DIRECTIONS = {"put": EP_PUT, "get": EP_GET}
 KF_MODES = {"record": KF_RECORD, "replay": KF_REPLAY}
 KF_DIRECTIONS = {"put": KF_PUT, "get": KF_GET}
+KF_STORAGES = ("native", "q8")
 SUPPORTED_HEAD_DIMS = (40, 64, 80, 160)
 
 
@@ -809,7 +810,10 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
         if seg_arr is not None:
             raise ValueError("key-frame stores belong to a self-attention call: no ip_segments")
         kcall, _kf_rows = _keyframe_call_args(kf, n, s, c, x.dtype)          # (_kf_rows: the host array kcall points at, kept alive)
-        nbytes = lib.aid_processor_kf_workspace_bytes(C.byref(a), C.byref(kcall))
+        # (the storage of the key-frame stores picks the entry point: the q8 one differs in its copy launch alone)
+        kf_size, kf_fwd, kf_name = (lib.aid_processor_kf_q8_workspace_bytes, lib.aid_processor_kf_q8_fwd, "aid_processor_kf_q8_fwd") \
+            if kf.get("storage", "native") == "q8" else (lib.aid_processor_kf_workspace_bytes, lib.aid_processor_kf_fwd, "aid_processor_kf_fwd")
+        nbytes = kf_size(C.byref(a), C.byref(kcall))
     else:
         nbytes = lib.aid_processor_workspace_bytes(C.byref(a))
     with _on(dev):
@@ -819,7 +823,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
             if est is not None:
                 _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
             elif kcall is not None:
-                _lib.check(lib.aid_processor_kf_fwd(C.byref(a), C.byref(kcall), _stream()), "aid_processor_kf_fwd")
+                _lib.check(kf_fwd(C.byref(a), C.byref(kcall), _stream()), kf_name)
             else:
                 _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
             raise RuntimeError("aid_processor_workspace_bytes returned 0")
@@ -828,7 +832,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
         if est is not None:
             _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
         elif kcall is not None:
-            _lib.check(lib.aid_processor_kf_fwd(C.byref(a), C.byref(kcall), _stream()), "aid_processor_kf_fwd")
+            _lib.check(kf_fwd(C.byref(a), C.byref(kcall), _stream()), kf_name)
         elif seg_arr is not None:
             _lib.check(lib.aid_processor_ip_fwd(C.byref(a), C.addressof(seg_arr), len(seg_arr), _stream()), "aid_processor_ip_fwd")
         else:
@@ -913,10 +917,26 @@ def processor_ep_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
 
 
 # ---- key-frame K / V^T stores (aid_hip.h: aid_keyframe_rows, aid_processor_kf_fwd) --------------------------------------------------
-def _keyframe_row_array(entries, step: torch.Tensor, k_fs: int, vt_fs: int, dtype: torch.dtype):
+def q8_block_bytes(n: int) -> int:
+    """Bytes of one block row of ``n`` elements in a q8 key-frame store (``aid_q8_block_bytes``): n int8, one exponent byte per 32
+    elements, rounded up to 16 bytes; 0 for an ``n`` that is no positive multiple of 8."""
+    n = int(n)
+    return 0 if n < 8 or n % 8 else (n + (n + 31) // 32 + 15) // 16 * 16
+
+
+def _check_storage(storage) -> str:
+    if storage not in KF_STORAGES:
+        raise ValueError(f"storage must be 'native' or 'q8'; got {storage!r}")
+    return storage
+
+
+def _keyframe_row_array(entries, step: torch.Tensor, k_fs: int, vt_fs: int, dtype: torch.dtype, storage: str = "native"):
     """The host array of AidKeyframeRow for ``entries`` = [(k_store [n_steps, k_fs], vt_store [n_steps, vt_fs], row), ...]; returns
-    (array, n_steps).  Every key frame's store is its own allocation; all hold the same number of steps."""
+    (array, n_steps).  Every key frame's store is its own allocation; all hold the same number of steps.  ``storage`` "q8": the stores
+    are uint8 [n_steps, q8_block_bytes(k_fs)] / [n_steps, q8_block_bytes(vt_fs)]."""
     entries = list(entries)
+    if storage == "q8":
+        dtype, k_fs, vt_fs = torch.uint8, q8_block_bytes(k_fs), q8_block_bytes(vt_fs)
     if not 1 <= len(entries) <= KF_MAX_ROWS:
         raise ValueError(f"one launch moves 1 .. {KF_MAX_ROWS} key-frame rows; got {len(entries)}")
     arr = (AidKeyframeRow * len(entries))()
@@ -924,6 +944,8 @@ def _keyframe_row_array(entries, step: torch.Tensor, k_fs: int, vt_fs: int, dtyp
     for i, (k_store, vt_store, row) in enumerate(entries):
         _require_gpu(k_store, vt_store)
         if k_store.dtype != dtype or vt_store.dtype != dtype:
+            if storage == "q8":
+                raise TypeError(f"the key-frame store holds {k_store.dtype}, a q8 store holds {dtype} block rows")
             raise TypeError(f"the key-frame store holds {k_store.dtype}, the call computes in {dtype}")
         ns = k_store.shape[0]
         if k_store.ndim != 2 or vt_store.ndim != 2 or tuple(k_store.shape) != (ns, k_fs) or tuple(vt_store.shape) != (ns, vt_fs) \
@@ -951,7 +973,7 @@ def _keyframe_call_args(kf: dict, n_frames: int, l: int, c: int, dtype: torch.dt
         raise ValueError(f"a replay takes exactly two key-frame stores (begin, end); got {len(entries)}")
     if mode == KF_RECORD and len({r_ for _, _, r_ in entries}) != len(entries):
         raise ValueError("the recorded rows must be distinct")
-    arr, n_steps = _keyframe_row_array(entries, kf["step"], k_fs, vt_fs, dtype)
+    arr, n_steps = _keyframe_row_array(entries, kf["step"], k_fs, vt_fs, dtype, _check_storage(kf.get("storage", "native")))
     call = AidKeyframeCall()
     call.rows, call.step, call.n_rows, call.n_steps, call.mode = arr, kf["step"].data_ptr(), len(arr), n_steps, mode
     return call, arr
@@ -979,11 +1001,36 @@ def keyframe_rows(k: torch.Tensor, vt: torch.Tensor, entries, step: torch.Tensor
         _lib.check(_lib.load().aid_keyframe_rows(C.byref(a), _stream()), "aid_keyframe_rows")
 
 
+def keyframe_rows_q8(k: torch.Tensor, vt: torch.Tensor, entries, step: torch.Tensor, direction: str, vt_cols: Optional[int] = None) -> None:
+    """``keyframe_rows`` with 8-bit block stores (``aid_keyframe_rows_q8``): "put" quantises rows of k [F, L, C] / vt [F, C, Lp] into
+    slot ``step[0]`` of ``entries`` = [(k_store uint8 [n_steps, q8_block_bytes(L C)], vt_store uint8 [n_steps, q8_block_bytes(C Lp)],
+    row), ...], "get" dequantises them back.  Of every vt row the first ``vt_cols`` columns (default: all Lp) are stored; the others
+    are pad — never read, +0 after "get".  LOSSY: per block of 32 elements |y - x| <= 2^(e-1) < max|x| / 127 (include/aid_hip.h)."""
+    dev = _require_gpu(k, vt)
+    if k.dtype != vt.dtype or k.ndim != 3 or vt.ndim != 3 or not k.is_contiguous() or not vt.is_contiguous() or k.shape[0] != vt.shape[0]:
+        raise ValueError("k [F, L, C] and vt [F, C, Lp] must be contiguous tensors of one dtype with the same number of rows")
+    f = k.shape[0]
+    a = AidKeyframeRowsQ8()
+    a.k_fs, a.vt_fs = k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2]
+    a.vt_ld, a.vt_cols = vt.shape[2], vt.shape[2] if vt_cols is None else int(vt_cols)
+    arr, a.n_steps = _keyframe_row_array([(k_, v_, int(r_) % f) for k_, v_, r_ in entries], step, a.k_fs, a.vt_fs, k.dtype, "q8")
+    a.k, a.vt, a.rows, a.step, a.n_rows = k.data_ptr(), vt.data_ptr(), arr, step.data_ptr(), len(arr)
+    try:
+        a.direction = KF_DIRECTIONS[direction]
+    except (KeyError, TypeError):
+        raise ValueError(f"direction must be 'put' or 'get'; got {direction!r}") from None
+    a.dtype = _dtype_code(k)
+    with _on(dev):
+        _lib.check(_lib.load().aid_keyframe_rows_q8(C.byref(a), _stream()), "aid_keyframe_rows_q8")
+
+
 def processor_kf_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, wo: torch.Tensor,
                      bo: Optional[torch.Tensor], heads: int, *, kf: dict, **kwargs) -> torch.Tensor:
     """A SELF-attention processor call with key-frame stores of its layer beside it (``aid_processor_kf_fwd``) — still one library
     call.  ``kf`` = dict(entries=[(k_store [n_steps, S C], vt_store [n_steps, C round_up(S, 8)], row), ...], step=int32 device [1],
-    mode="record" | "replay"); every other keyword is ``processor_fwd``'s.
+    mode="record" | "replay"[, storage="native" | "q8"]); every other keyword is ``processor_fwd``'s.  With ``storage="q8"`` the stores
+    are the uint8 block stores of ``keyframe_rows_q8`` and the call is ``aid_processor_kf_q8_fwd``: the same call with the quantising /
+    dequantising copy launch (lossy; "record" still returns ``y`` bit for bit).
     "record": a ``mode="plain"`` call over a batch that holds the key frames — ``processor_fwd`` itself, ``y`` bit for bit — plus rows
     ``row`` of this step's k / V^T put into slot ``step[0]`` of their stores (1 .. 8 entries, distinct rows).  "replay": an
     interpolated call; ``x`` holds the LOCAL frames only (interior coefficients, PLAIN riders), the two entries are the begin and the

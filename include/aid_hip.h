@@ -600,6 +600,57 @@ size_t aid_processor_kf_workspace_bytes(const AidProcessorArgs* args /* host */,
 int    aid_processor_kf_fwd(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Key-frame store in 8-bit blocks, "q8" (no ABI version change: four new entry points, no existing struct, constant or entry point
+ * changes).  LOSSY and opt-in: a key frame's K / V^T are written once and read many times, and enter a replay only as the two
+ * end-point key segments.  A *block row* of n elements (one k block, n = k_fs, or one V^T block, n = vt_fs; n a positive multiple of
+ * 8) is stored as aid_q8_block_bytes(n) = round_up(n + ceil(n / 32), 16) bytes:
+ *   bytes [0, n)                    int8 elements
+ *   bytes [n, n + ceil(n / 32))     one exponent byte per block of 32 consecutive elements (the last block may hold 8, 16 or 24)
+ *   the rest up to the 16-byte boundary is never read and never written.
+ * Stored elements: every element of a k block; of a V^T block — vt_fs / vt_ld rows of vt_ld columns — the first vt_cols columns of
+ * every row.  Columns >= vt_cols are pad: they are never read into arithmetic (they may hold NaN), their int8 is 0, they take no part
+ * in a block's maximum, and GET writes +0 there (nothing reads those columns: the contract of aid_attn_fwd).
+ * Per block, with a = max |x| over its stored elements (exact, in fp32): e is the smallest integer with 127 * 2^e >= a, clamped to
+ * [-126, 120] (-126 when a == 0 or the block stores nothing); the exponent byte is e + 127; every element is
+ * q = clamp(rne(x * 2^-e), -127, 127), round-half-to-even, the product exact in fp32.  The value that comes back is q * 2^e converted
+ * to the element type — exact in f16, bf16 and f32 — so |y - x| <= 2^(e-1) < a / 127 for every stored element, and a block of f16
+ * subnormals comes back unchanged.  Non-finite stored elements are outside the contract: the values that come back are unspecified,
+ * the bytes read and written are the ones stated.
+ * aid_keyframe_rows_q8 is aid_keyframe_rows with such stores, k_store_i [n_steps, aid_q8_block_bytes(k_fs)] and vt_store_i
+ * [n_steps, aid_q8_block_bytes(vt_fs)] bytes, in ONE streaming launch.  For entry i, with B(n) = n + ceil(n / 32):
+ *   AID_KF_PUT  reads  k[row_i * k_fs .. + k_fs), vt[row_i * vt_fs .. + vt_fs) and *step;
+ *               writes bytes [0, B(k_fs)) of block row *step of k_store_i and bytes [0, B(vt_fs)) of block row *step of vt_store_i
+ *   AID_KF_GET  reads what PUT writes (and *step), writes what PUT reads.  Nothing else is read or written.
+ * A *step outside [0, n_steps) moves nothing.  Everything aid_keyframe_rows checks is checked; in addition vt_ld % 8 != 0,
+ * vt_fs % vt_ld != 0 or vt_cols outside 1 .. vt_ld is AID_ERR_SHAPE, and the stores are 16-byte aligned (AID_ERR_SHAPE) — all before
+ * any launch.  A lane moves one 16-byte chunk of the call tensor and 8 (f16 / bf16) or 4 (f32) store bytes; the 4 or 8 lanes of a block
+ * agree on its maximum by lane exchange; no atomics, no LDS.
+ * aid_processor_kf_q8_fwd is aid_processor_kf_fwd with that launch as the copy step (vt_ld = round_up(s, 8), vt_cols = s): RECORD —
+ * y bit-identical to aid_processor_fwd, the call's k / V^T not modified, the workspace equal; REPLAY — rows n_frames / n_frames + 1
+ * are filled by the dequantising GET (pad columns +0), the rest of the call is unchanged.  Every refusal of aid_processor_kf_fwd
+ * applies; aid_processor_kf_q8_workspace_bytes == aid_processor_kf_workspace_bytes.  f16 / bf16 / f32.
+ * ------------------------------------------------------------------------------------- */
+size_t aid_q8_block_bytes(int64_t n_elements);      /* 0 for n < 8 or n % 8 != 0 */
+
+typedef struct AidKeyframeRowsQ8 {
+    void*                 k;     /* [rows, k_fs]  of the call, element type `dtype`            */
+    void*                 vt;    /* [rows, vt_fs] of the call                                  */
+    const AidKeyframeRow* rows;  /* HOST: n_rows entries; k_store / vt_store are q8 stores:    */
+                                 /*   [n_steps, aid_q8_block_bytes(k_fs | vt_fs)] bytes        */
+    const int32_t*        step;  /* DEVICE: the slot index, read by the kernel                 */
+    int64_t k_fs, vt_fs;         /* block sizes = row strides of the call, in elements         */
+    int32_t vt_ld, vt_cols;      /* V^T rows of vt_ld columns, the first vt_cols stored        */
+    int32_t n_rows;              /* 1 .. AID_KF_MAX_ROWS                                       */
+    int32_t n_steps;
+    int32_t direction;           /* AID_KF_PUT / AID_KF_GET                                    */
+    int32_t dtype;               /* AID_DTYPE_*                                                */
+} AidKeyframeRowsQ8;
+
+int    aid_keyframe_rows_q8(const AidKeyframeRowsQ8* args /* host */, void* stream);
+size_t aid_processor_kf_q8_workspace_bytes(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */);
+int    aid_processor_kf_q8_fwd(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
