@@ -29,7 +29,7 @@ KF_RECORD, KF_REPLAY = 1, 2
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
-    "aid_gemm_nt", "aid_dora_gain", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
+    "aid_gemm_nt", "aid_dora_gain", "aid_cfg_rescale", "aid_layernorm", "aid_ln_stats", "aid_ln_fold", "aid_attn_fwd", "aid_lerp_kv", "aid_ip_attn_fwd", "aid_processor_workspace_bytes", "aid_processor_fwd", "aid_processor_ip_fwd",
     "aid_endpoint_rows", "aid_processor_ep_workspace_bytes", "aid_processor_ep_fwd",
     "aid_keyframe_rows", "aid_processor_kf_workspace_bytes", "aid_processor_kf_fwd",
     "aid_q8_block_bytes", "aid_keyframe_rows_q8", "aid_processor_kf_q8_workspace_bytes", "aid_processor_kf_q8_fwd",
@@ -209,6 +209,9 @@ def bind(path: str) -> C.CDLL:
     lib.aid_dora_gain.restype = C.c_int
     lib.aid_dora_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_void_p]
+    lib.aid_cfg_rescale.restype = C.c_int
+    lib.aid_cfg_rescale.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_float, C.c_float, C.c_int32, C.c_void_p]
     lib.aid_layernorm.restype = C.c_int
     lib.aid_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
                                   C.c_int32, C.c_void_p]

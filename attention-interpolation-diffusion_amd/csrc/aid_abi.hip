@@ -500,6 +500,43 @@ int aid_dora_gain(const void* w, const void* a_pack, const void* b_pack, const v
     return e == hipSuccess ? AID_OK : fail_hip(e, "aid_dora_gain");
 }
 
+int aid_cfg_rescale(const void* text, const void* uncond, void* out, int32_t n, int64_t e, int64_t text_stride, int64_t uncond_stride,
+                    int64_t out_stride, float guidance_scale, float guidance_rescale, int32_t dtype, void* stream) {
+    if (!text || !uncond || !out || n < 0) return AID_ERR_ARG;
+    if (!dtype_ok(dtype)) return AID_ERR_DTYPE;
+    if (e < 2) return AID_ERR_SHAPE;                                   // the unbiased std of one element is undefined
+    if (text_stride < e || uncond_stride < e || out_stride < e) return AID_ERR_ARG;
+    if (!(guidance_rescale >= 0.f && guidance_rescale <= 1.f)) return AID_ERR_ARG;
+    const int64_t es = dtype == AID_DTYPE_F32 ? 4 : 2;
+    const uintptr_t pt = reinterpret_cast<uintptr_t>(text), pu = reinterpret_cast<uintptr_t>(uncond), po = reinterpret_cast<uintptr_t>(out);
+    if ((pt | pu | po) % es) return AID_ERR_SHAPE;                     // (strides are in elements: every sample is aligned with its base)
+    if (n > 0) {
+        // out may BE an input (same base, same stride: every element is read before the same lane writes it); any other overlap of
+        // the bytes the call writes with the bytes it reads is refused
+        const uintptr_t in_p[2] = {pt, pu};
+        const int64_t in_s[2] = {text_stride, uncond_stride};
+        const uintptr_t o_end = po + (uintptr_t)(((int64_t)(n - 1) * out_stride + e) * es);
+        for (int i = 0; i < 2; ++i) {
+            if (in_p[i] == po && in_s[i] == out_stride) continue;
+            const uintptr_t i_end = in_p[i] + (uintptr_t)(((int64_t)(n - 1) * in_s[i] + e) * es);
+            if (po < i_end && in_p[i] < o_end) return AID_ERR_ARG;
+        }
+    }
+    if (n == 0) return AID_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AID_ERR_NO_DEVICE;
+    hipError_t err;
+    {
+        // traffic: text and uncond read, out written (the second and third walk of a sample hit L2)
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_cfg_rescale<%s>", dtype_name(dtype));
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 12.0 * n * (double)e, 3.0 * es * n * (double)e);
+        err = aid::cfg_rescale_launch(text, uncond, out, n, e, text_stride, uncond_stride, out_stride, guidance_scale, guidance_rescale,
+                                      dtype, static_cast<hipStream_t>(stream));
+    }
+    return err == hipSuccess ? AID_OK : fail_hip(err, "aid_cfg_rescale");
+}
+
 int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
     if (!args) return AID_ERR_ARG;
     const AidAttnArgs& a = *args;

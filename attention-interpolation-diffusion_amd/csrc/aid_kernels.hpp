@@ -216,6 +216,9 @@ hipError_t ln_fold_launch(const void* w, const void* gamma, const void* beta, vo
 // DoRA row gain (aid_dora.hip): gain[n] = magnitude[n] / ||W[n, :] + (B_pack A_pack)[n, :]||
 hipError_t dora_gain_launch(const void* w, const void* a_pack, const void* b_pack, const void* magnitude, float* gain, int n_out,
                             int n_in, int ldw, int rank, int dtype, hipStream_t stream);
+// classifier-free guidance + guidance rescale, one workgroup per sample (aid_cfg.hip); arguments checked by the caller
+hipError_t cfg_rescale_launch(const void* text, const void* uncond, void* out, int n, int64_t e, int64_t text_stride,
+                              int64_t uncond_stride, int64_t out_stride, float gs, float phi, int dtype, hipStream_t stream);
 bool       layernorm_width_supported(int c);
 
 }  // namespace aid

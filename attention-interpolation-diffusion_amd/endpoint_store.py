@@ -200,12 +200,17 @@ def _short(v) -> str:
     return s if len(s) <= 24 else s[:21] + "..."
 
 
-def run_settings(*, num_inference_steps: int, guidance_scale: float, dtype: torch.dtype, timesteps, unet, lora_scale=None) -> Dict[str, Any]:
+def run_settings(*, num_inference_steps: int, guidance_scale: float, dtype: torch.dtype, timesteps, unet, lora_scale=None,
+                 guidance_rescale: float = 0.0) -> Dict[str, Any]:
     """The settings of a run that an end point's own trajectory depends on (shared with keyframe_store.py): the settings themselves,
-    the float32 precision codes in force, the LoRA adapters' state and the identity of the UNet."""
+    the float32 precision codes in force, the LoRA adapters' state and the identity of the UNet.  A non-zero ``guidance_rescale``
+    changes the trajectory like the guidance scale does and rides in its entry: the pair ``(guidance_scale, guidance_rescale)``
+    instead of the bare scale."""
     ts = timesteps.detach().to("cpu").tolist() if torch.is_tensor(timesteps) else [float(t) for t in timesteps]
     return {
-        "num_inference_steps": int(num_inference_steps), "guidance_scale": float(guidance_scale), "dtype": str(dtype),
+        "num_inference_steps": int(num_inference_steps),
+        "guidance_scale": float(guidance_scale) if float(guidance_rescale) == 0.0 else (float(guidance_scale), float(guidance_rescale)),
+        "dtype": str(dtype),
         "f32_precision": (ops.f32_split_code(), ops.f32_attn_split_code()) if dtype == torch.float32 else (0, 0),
         "timesteps": tuple(ts), "lora": (lora_state(unet), None if lora_scale is None else float(lora_scale)),
         "unet": (type(unet).__name__, id(unet)),
@@ -215,7 +220,7 @@ def run_settings(*, num_inference_steps: int, guidance_scale: float, dtype: torc
 def run_signature(*, latent_start, latent_end, embeds_start, embeds_end, embeds_negative: List[Optional[torch.Tensor]],
                   embeds_pooled: List[Optional[torch.Tensor]], embeds_guide: List[Optional[torch.Tensor]], num_inference_steps: int,
                   warmup_ratio: float, early: str, late: str, fusion: bool, guidance_scale: float, dtype: torch.dtype, timesteps,
-                  unet, lora_scale=None) -> Dict[str, Any]:
+                  unet, lora_scale=None, guidance_rescale: float = 0.0) -> Dict[str, Any]:
     """The signature a pipeline run records / replays under (``SIGNATURE_FIELDS``): content digests of the tensors, the settings
     themselves, the float32 precision codes in force, the LoRA adapters' state and the identity of the UNet."""
     sig = {
@@ -225,6 +230,6 @@ def run_signature(*, latent_start, latent_end, embeds_start, embeds_end, embeds_
         "embeds_guide": tensor_digest(*embeds_guide), "warmup_ratio": float(warmup_ratio),
         "early": str(early), "late": str(late), "fusion": bool(fusion),
         **run_settings(num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, dtype=dtype, timesteps=timesteps,
-                       unet=unet, lora_scale=lora_scale),
+                       unet=unet, lora_scale=lora_scale, guidance_rescale=guidance_rescale),
     }
     return {f: sig[f] for f in SIGNATURE_FIELDS}

@@ -167,7 +167,8 @@ class AidDenoiseLoop:
 
     def __init__(self, unet, sample, cond, uncond, num_inference_steps: int = 50, warmup_ratio: float = 0.5,
                  guidance_scale: float = 7.5, use_graphs: bool = True, combine: Optional[Callable] = None,
-                 batched_cfg: bool = False, ctx_index: Optional[Sequence[int]] = None, concurrent_cfg: bool = False):
+                 batched_cfg: bool = False, ctx_index: Optional[Sequence[int]] = None, concurrent_cfg: bool = False,
+                 guidance_rescale: float = 0.0):
         """``batched_cfg``: run the conditional and the unconditional pass of a step as ONE UNet call over the
         batch [cond frames ; uncond frames] (how stock diffusers pipelines do classifier-free guidance).  The
         AID processors treat the second half as plain riders (negative coefficients), so the result equals the
@@ -179,6 +180,8 @@ class AidDenoiseLoop:
         """``concurrent_cfg``: when the two passes of a step cannot share one UNet call (IP-Adapter contexts), run them as two UNet
         calls on two STREAMS — forked and joined inside one hipGraph when ``use_graphs`` — instead of back to back: the passes are
         independent, every kernel of one overlaps the other's (half the rows per kernel, both halves in flight).  Same results."""
+        """``guidance_rescale`` > 0: the default combine rescales the guided output of every frame to the text pass's spread
+        (pipeline_interpolated_sd.py:92-108, 1892-1902) — guidance and rescale in one launch (``ops.cfg_rescale``), in every layout."""
         self.unet, self.sample, self.cond, self.uncond = unet, sample, cond, uncond
         self.batched_cfg = batched_cfg
         self.concurrent_cfg = concurrent_cfg and not batched_cfg
@@ -203,6 +206,9 @@ class AidDenoiseLoop:
         self.num_inference_steps = num_inference_steps
         self.warmup_steps = int(num_inference_steps * warmup_ratio)        # pipeline_interpolated_sd.py:1831
         self.guidance_scale = guidance_scale
+        self.guidance_rescale = float(guidance_rescale)
+        if not 0.0 <= self.guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale must be in [0, 1]; got {guidance_rescale}")
         self.use_graphs = use_graphs
         self.combine = combine or self._cfg
         self._graphs: Dict[Tuple[str, int], torch.cuda.CUDAGraph] = {}
@@ -215,7 +221,10 @@ class AidDenoiseLoop:
 
     def _cfg(self, text, uncond):
         if isinstance(text, dict):
-            return {k: uncond[k] + self.guidance_scale * (text[k] - uncond[k]) for k in text}
+            return {k: self._cfg(text[k], uncond[k]) for k in text}
+        if self.guidance_rescale > 0.0:
+            from . import ops
+            return ops.cfg_rescale(text, uncond, self.guidance_scale, self.guidance_rescale)
         return uncond + self.guidance_scale * (text - uncond)
 
     # -- the three distinct passes ---------------------------------------------------------------

@@ -433,6 +433,44 @@ def dora_gain(w: torch.Tensor, a_pack: torch.Tensor, b_pack: torch.Tensor, magni
     return gain
 
 
+def _sample_layout(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(n, e, sample stride in elements) of ``t`` [n, ...] whose samples are contiguous blocks of e elements (dim 0 may be strided)."""
+    if t.ndim < 2:
+        raise ValueError(f"{what} must be [n, ...] (one sample per row of dim 0); got shape {tuple(t.shape)}")
+    n = t.shape[0]
+    e = t.numel() // n if n else int(torch.Size(t.shape[1:]).numel())
+    expect = 1
+    for size, stride in zip(reversed(t.shape[1:]), reversed(t.stride()[1:])):
+        if size != 1 and stride != expect:
+            raise ValueError(f"{what}: the elements of a sample must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+        expect *= size
+    return n, e, (t.stride(0) if n > 1 else e)
+
+
+def cfg_rescale(text: torch.Tensor, uncond: torch.Tensor, guidance_scale: float, guidance_rescale: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Classifier-free guidance with guidance rescale in one launch (``aid_cfg_rescale``; pipeline_interpolated_sd.py:92-108,
+    1892-1902): per sample ``c = uncond + gs (text - uncond)``, ``out = c (rescale std(text) / std(c) + 1 - rescale)``, fp32 arithmetic,
+    one rounding.  ``text`` / ``uncond`` / ``out`` [n, ...] of one shape and dtype (float16 / bfloat16 / float32); dim 0 may be strided
+    (the two halves of a batched ``[2 n, ...]`` UNet output are passed as views, no copy), the elements of a sample are contiguous.
+    ``out`` may be ``text`` or ``uncond`` itself; it is allocated when None.  Enqueues on the current stream: capturable."""
+    dev = _require_gpu(text, uncond, out)
+    dt = _dtype_code(text)
+    if out is None:
+        out = torch.empty(text.shape, dtype=text.dtype, device=text.device)
+    if uncond.shape != text.shape or out.shape != text.shape or uncond.dtype != text.dtype or out.dtype != text.dtype:
+        raise ValueError("cfg_rescale takes text, uncond and out of one shape and dtype")
+    n, e, ts = _sample_layout(text, "text")
+    _, _, us = _sample_layout(uncond, "uncond")
+    _, _, os_ = _sample_layout(out, "out")
+    if n == 0:
+        return out
+    with _on(dev):
+        _lib.check(_lib.load().aid_cfg_rescale(text.data_ptr(), uncond.data_ptr(), out.data_ptr(), n, e, ts, us, os_,
+                                               float(guidance_scale), float(guidance_rescale), dt, _stream()), "aid_cfg_rescale")
+    return out
+
+
 def project_kv(e: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, extra_rows: int = 0,
                lora_k: Optional[Tuple[torch.Tensor, ...]] = None,
                lora_v: Optional[Tuple[torch.Tensor, ...]] = None,

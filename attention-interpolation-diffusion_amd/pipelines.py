@@ -33,6 +33,7 @@ a guide-prompt run share one projected text context (``ctx_index``).
 """
 from __future__ import annotations
 
+import inspect
 import warnings
 
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
@@ -56,9 +57,12 @@ from .sequence import SequenceBatch, prepare_sequence, prepare_single
 # components used where diffusers is absent
 # ---------------------------------------------------------------------------------------------
 class DDIMSchedulerLite:
-    """Deterministic DDIM (eta = 0) on the scaled-linear beta schedule of SD / SDXL — the published update
-    x_{t-1} = sqrt(a_{t-1}) x0 + sqrt(1 - a_{t-1}) eps with x0 = (x_t - sqrt(1 - a_t) eps) / sqrt(a_t) — behind the
-    diffusers scheduler interface the pipelines use (third-party there; north_star names 50-step DDIM)."""
+    """DDIM on the scaled-linear beta schedule of SD / SDXL — the published update
+    x_{t-1} = sqrt(a_{t-1}) x0 + sqrt(1 - a_{t-1} - s^2) eps + s z with x0 = (x_t - sqrt(1 - a_t) eps) / sqrt(a_t) and
+    s^2 = eta^2 (1 - a_{t-1}) / (1 - a_t) (1 - a_t / a_{t-1}) (Song et al. 2021, eq. 12 and 16; deterministic at the default eta = 0)
+    — behind the diffusers scheduler interface the pipelines use (third-party there; north_star names 50-step DDIM).
+    ``set_timesteps(timesteps=[...])`` takes a custom table (descending integers in [0, num_train_timesteps)); there is no
+    ``sigmas`` keyword, as on diffusers' DDIMScheduler."""
     order = 1
     init_noise_sigma = 1.0
 
@@ -70,8 +74,26 @@ class DDIMSchedulerLite:
         self.steps_offset = steps_offset
         self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
         self.num_inference_steps = num_train_timesteps
+        self._prev: Optional[Dict[int, int]] = None        # custom table: timestep -> the next one (-1 behind the last)
 
-    def set_timesteps(self, num_inference_steps: int, device=None):
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps: Optional[Sequence[int]] = None):
+        if timesteps is not None:
+            if num_inference_steps is not None:
+                raise ValueError("pass num_inference_steps or timesteps, not both")
+            tl = timesteps.tolist() if torch.is_tensor(timesteps) else list(timesteps)
+            if not tl or any(int(t) != t for t in tl):
+                raise ValueError("timesteps must be a non-empty list of integers")
+            tl = [int(t) for t in tl]
+            if any(a <= b for a, b in zip(tl, tl[1:])) or tl[-1] < 0 or tl[0] >= self.num_train_timesteps:
+                raise ValueError(f"timesteps must be descending integers in [0, {self.num_train_timesteps}); got {tl}")
+            ts = torch.tensor(tl, dtype=torch.int64)
+            self.timesteps = ts.to(device) if device is not None else ts
+            self.num_inference_steps = len(tl)
+            self._prev = dict(zip(tl, tl[1:] + [-1]))
+            return
+        if num_inference_steps is None:
+            raise ValueError("pass num_inference_steps or timesteps")
+        self._prev = None
         ratio = self.num_train_timesteps // num_inference_steps
         ts = (torch.arange(0, num_inference_steps) * ratio).flip(0) + self.steps_offset      # "leading" spacing
         self.timesteps = ts.to(device) if device is not None else ts
@@ -80,16 +102,22 @@ class DDIMSchedulerLite:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
-    def step(self, model_output, timestep, sample, return_dict: bool = False, **kwargs):
+    def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, return_dict: bool = False, **kwargs):
         t = int(timestep)
-        prev = t - self.num_train_timesteps // self.num_inference_steps
+        prev = t - self.num_train_timesteps // self.num_inference_steps if self._prev is None else self._prev[t]
         a_t = self.alphas_cumprod[t]
         a_p = self.alphas_cumprod[prev] if prev >= 0 else torch.tensor(1.0, dtype=torch.float64)
         a_t, a_p = float(a_t), float(a_p)
         eps = model_output.to(torch.float32)
         x = sample.to(torch.float32)
         x0 = (x - (1 - a_t) ** 0.5 * eps) / a_t ** 0.5
-        out = (a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * eps).to(sample.dtype)
+        if eta == 0.0:
+            out = (a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * eps).to(sample.dtype)
+            return (out,)
+        var = float(eta) ** 2 * (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+        gdev = generator.device if generator is not None else sample.device       # a host generator seeds a device run, as in diffusers
+        z = torch.randn(sample.shape, generator=generator, device=gdev, dtype=torch.float32).to(sample.device)
+        out = (a_p ** 0.5 * x0 + max(1 - a_p - var, 0.0) ** 0.5 * eps + var ** 0.5 * z).to(sample.dtype)
         return (out,)
 
 
@@ -244,6 +272,52 @@ def _use_graphs(flag: Optional[bool], device: torch.device) -> bool:
     return (device.type == "cuda" and torch.cuda.is_available()) if flag is None else bool(flag)
 
 
+def _retrieve_timesteps(scheduler, num_inference_steps: Optional[int], device, timesteps=None, sigmas=None) -> Tuple[Any, int]:
+    """``scheduler.set_timesteps`` with a custom ``timesteps`` or ``sigmas`` table where one is given (pipeline_interpolated_sd.py:111-154,
+    called at :1716): returns ``(scheduler.timesteps, len(scheduler.timesteps))``.  Both given, or a scheduler whose ``set_timesteps``
+    lacks the keyword, raises ``ValueError``."""
+    if timesteps is not None and sigmas is not None:
+        raise ValueError("pass only one of `timesteps` and `sigmas` to set a custom schedule")
+    for name, table in (("timesteps", timesteps), ("sigmas", sigmas)):
+        if table is None:
+            continue
+        if name not in inspect.signature(scheduler.set_timesteps).parameters:
+            raise ValueError(f"{type(scheduler).__name__}.set_timesteps takes no `{name}`: this scheduler does not support a custom "
+                             f"{name} schedule")
+        scheduler.set_timesteps(device=device, **{name: table})
+        return scheduler.timesteps, len(scheduler.timesteps)
+    scheduler.set_timesteps(num_inference_steps, device=device)
+    return scheduler.timesteps, num_inference_steps
+
+
+def _extra_step_kwargs(scheduler, eta: float, generator) -> Dict[str, Any]:
+    """``eta`` / ``generator`` for ``scheduler.step``, each only where its signature accepts it (pipeline_interpolated_sd.py:782-795): not
+    every scheduler is DDIM."""
+    accepted = inspect.signature(scheduler.step).parameters
+    extra: Dict[str, Any] = {}
+    if "eta" in accepted:
+        extra["eta"] = eta
+    if "generator" in accepted:
+        extra["generator"] = generator
+    return extra
+
+
+def _check_rescale(guidance_rescale: float) -> float:
+    r = float(guidance_rescale)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"guidance_rescale must be in [0, 1]; got {guidance_rescale}")
+    return r
+
+
+def _guided_noise(noise_text: torch.Tensor, noise_unc: torch.Tensor, gs: float, rescale: float) -> torch.Tensor:
+    """Classifier-free guidance (pipeline_interpolated_sd.py:1892) and, with ``rescale > 0`` (:1896-1902), the guidance rescale: then
+    both in one launch of the library (``ops.cfg_rescale``: the two noise tensors may be the halves of one batched output).  With
+    ``rescale == 0`` the torch expression the loops have always run."""
+    if rescale > 0.0:
+        return ops.cfg_rescale(noise_text, noise_unc, gs, rescale)
+    return noise_unc + gs * (noise_text - noise_unc)
+
+
 def _dev_scalar(t, device: torch.device) -> torch.Tensor:
     """The step's timestep as a device tensor (graph input); schedulers hand out device or host scalars."""
     if torch.is_tensor(t):
@@ -265,6 +339,7 @@ class InterpolationStableDiffusionPipeline:
         self._encode_prompt, self._encode_image = encode_prompt, encode_image
         self.vae_scaling_factor = vae_scaling_factor
         self._guidance_scale = self.default_guidance_scale
+        self._guidance_rescale = 0.0
         self._aid_early: Optional[str] = None
 
     # -- wrapping a loaded diffusers pipeline (only where diffusers is importable) -----------------
@@ -353,6 +428,10 @@ class InterpolationStableDiffusionPipeline:
         return self._guidance_scale
 
     @property
+    def guidance_rescale(self):
+        return self._guidance_rescale
+
+    @property
     def do_classifier_free_guidance(self):
         return self._guidance_scale > 1
 
@@ -422,17 +501,22 @@ class InterpolationStableDiffusionPipeline:
         ``endpoints`` (build-specific): an :class:`EndpointStore`.  Empty, the run RECORDS the two end points into it (a normal run,
         bit-identical outputs); recorded under the same end points and settings, the run REPLAYS: only the frame at ``it`` goes
         through the UNet, its AID steps attend to the stored end-point keys / values, and the end points' outputs come from the
-        stored latents — the return value has the usual three frames.  Anything else raises ``ValueError`` naming what differs."""
+        stored latents — the return value has the usual three frames.  Anything else raises ``ValueError`` naming what differs.
+        ``timesteps`` / ``sigmas``: a custom schedule handed to ``scheduler.set_timesteps`` (:111-154, :1716); the step count and the
+        warm-up count ``int(T * warmup_ratio)`` then follow the table's length.  ``eta`` / ``generator`` reach ``scheduler.step`` where
+        its signature takes them (:782-795); ``eta != 0`` with ``endpoints`` raises.  ``guidance_rescale`` > 0 (:1896-1902): the guided
+        noise of every step is rescaled to the text pass's spread (arXiv 2305.08891 §3.4), in one launch with the guidance itself."""
         if image_start is not None and image_end is None:
             raise ValueError("Please provide both `image_start` and `image_end` to interpolate, or only `image_end` to "
                              "control the scale.")                                     # pipeline_interpolated_sd.py:1608-1612
         if (image_start is not None or image_end is not None) and self._encode_image is None:
             raise ValueError("image inputs need an `encode_image` component; pass image_embeds_start / image_embeds_end")
-        if timesteps is not None or sigmas is not None or eta != 0.0 or guidance_rescale != 0.0:
-            raise NotImplementedError("custom timesteps / sigmas / eta / guidance_rescale are the scheduler's (third-party) "
-                                      "business; configure the scheduler component instead")
+        if eta != 0.0 and endpoints is not None:
+            raise ValueError("eta != 0 with an end-point store: a stochastic trajectory cannot be recorded once and replayed (run with "
+                             "eta = 0, or without `endpoints`)")
+        gr = _check_rescale(guidance_rescale)
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
-        self._guidance_scale = gs
+        self._guidance_scale, self._guidance_rescale = gs, gr
         dev, dtype = self._unet_device_dtype()
         cak = cross_attention_kwargs
         ls = cak.get("scale", None) if cak is not None else None
@@ -450,7 +534,8 @@ class InterpolationStableDiffusionPipeline:
                                None if guide is None else guide[0][0], None if guide is None else guide[1][0], init=init)
         pooled = self._pooled_single(cond_s, cond_e, unc_s, unc_e, guide, it, init)
         img = self._image_embeds_single(image_start, image_end, image_embeds_start, image_embeds_end, it, init, dev, dtype)
-        self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        _, num_inference_steps = _retrieve_timesteps(self.scheduler, num_inference_steps, dev, timesteps, sigmas)      # :1716
+        extra_step_kwargs = _extra_step_kwargs(self.scheduler, eta, generator)         # :1750
         warmup_steps = int(num_inference_steps * warmup_ratio)                         # :1831
         lat = batch.latents
         cond, unc = batch.cond.to(dev, dtype), batch.uncond.to(dev, dtype)
@@ -467,7 +552,7 @@ class InterpolationStableDiffusionPipeline:
                                 embeds_guide=[] if guide is None else [g_ for pair in guide for g_ in pair],
                                 num_inference_steps=num_inference_steps, warmup_ratio=warmup_ratio, early=early_mode, late="self",
                                 fusion=fusion, guidance_scale=gs, dtype=dtype, timesteps=self.scheduler.timesteps, unet=self.unet,
-                                lora_scale=ls)
+                                lora_scale=ls, guidance_rescale=gr)
             if endpoints.recorded:
                 endpoints.begin_replay(sig, dev)
                 ep_mode, n_run = "replay", 1
@@ -508,8 +593,8 @@ class InterpolationStableDiffusionPipeline:
                 noise_text = graphs.run(key, cond_pass, x=x, t=td)
                 self.deactivate_aid()                                                      # :1870
                 noise_unc = graphs.run(("uncond",), uncond_pass, x=x, t=td)
-                noise = noise_unc + gs * (noise_text - noise_unc)                          # :1892
-                lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
+                noise = _guided_noise(noise_text, noise_unc, gs, gr)                       # :1892-1902
+                lat = self.scheduler.step(noise, t, lat, **extra_step_kwargs, return_dict=False)[0]        # :1905-1907
                 if callback_on_step_end is not None:
                     out = callback_on_step_end(self, i, t, {"latents": lat}) or {}
                     lat = out.pop("latents", lat)
@@ -534,7 +619,8 @@ class InterpolationStableDiffusionPipeline:
                     # build-specific
                     embeds_start=None, embeds_end=None, embeds_guide=None, batched_cfg: bool = True,
                     output_type: str = "np", coef: Optional[Sequence[float]] = None, use_graphs: Optional[bool] = None,
-                    cross_attention_kwargs: Optional[Dict[str, Any]] = None, endpoints: Optional[EndpointStore] = None):
+                    cross_attention_kwargs: Optional[Dict[str, Any]] = None, endpoints: Optional[EndpointStore] = None,
+                    guidance_rescale: float = 0.0):
         """gradio_src/pipeline_interpolated_stable_diffusion.py:163-304 with the root pipelines' warm-up count
         (``i < int(T * warmup_ratio)`` with 0-based ``i``).  ``late`` must be "self" (plain
         attention) or one of the AID modes.  ``batched_cfg``: the two passes of a step run as one UNet call.
@@ -542,11 +628,13 @@ class InterpolationStableDiffusionPipeline:
         ``interpolate_single(t_k)`` would — latents slerp'd and embeddings lerp'd at ``t_k``, attention coefficient
         ``t_k`` — in one N-frame run (the Beta-prior exploration fills several gaps per run with it, prior.py).
         ``use_graphs``, ``cross_attention_kwargs`` and ``endpoints`` as in ``interpolate_single`` (a replay renders the ``size - 2``
-        interior frames; a store recorded by either method replays in the other).  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
+        interior frames; a store recorded by either method replays in the other); ``guidance_rescale`` (build-specific here) as in
+        ``interpolate_single``.  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
         back when the run ends (the run works with its own N-frame processors)."""
         if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
             raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
+        gr = _check_rescale(guidance_rescale)
         dev, dtype = self._unet_device_dtype()
         cak = cross_attention_kwargs
         ls = cak.get("scale", None) if cak is not None else None
@@ -585,7 +673,7 @@ class InterpolationStableDiffusionPipeline:
                                 embeds_guide=[] if guide is None else [g_ for pair in guide for g_ in pair],
                                 num_inference_steps=num_inference_steps, warmup_ratio=warmup_ratio,
                                 early=early.split("_")[1], late=late, fusion=early.startswith("fused"), guidance_scale=gs, dtype=dtype,
-                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls)
+                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls, guidance_rescale=gr)
             if endpoints.recorded:
                 endpoints.begin_replay(sig, dev)
                 ep_mode = "replay"
@@ -652,7 +740,7 @@ class InterpolationStableDiffusionPipeline:
                     noise_text = graphs.run(("cond",) + gkey, cond_pass, x=x, t=td)
                     set_aid_active(self.unet, False)
                     noise_unc = graphs.run(("uncond",) + gkey, uncond_pass, x=x, t=td)
-                noise = noise_unc + gs * (noise_text - noise_unc)
+                noise = _guided_noise(noise_text, noise_unc, gs, gr)
                 lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
             if ep_mode == "record":
                 endpoints.finish_record(torch.cat([lat[0:1], lat[-1:]]))
@@ -671,7 +759,7 @@ class InterpolationStableDiffusionPipeline:
                          embeds: Optional[Sequence[tuple]] = None, negative_prompt: str = "", num_inference_steps: int = 25,
                          warmup_ratio: float = 0.5, aid_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
                          use_graphs: Optional[bool] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
-                         output_type: str = "np"):
+                         output_type: str = "np", guidance_rescale: float = 0.0):
         """Denoise the K key frames ``names`` as ONE plain classifier-free-guidance batch (``latents`` [K, C, h, w] or K tensors
         [1, C, h, w]; ``prompts`` or ``embeds``, one per frame, as ``interpolate`` takes ``prompt_start`` / ``embeds_start``) and record
         them into ``store``: at every self-attention layer of the conditional pass of the first ``aid_steps`` steps (default
@@ -679,7 +767,8 @@ class InterpolationStableDiffusionPipeline:
         goes into its own store — one PUT launch beside the projections — and each frame's inputs and final latent are kept.  That is
         everything ``interpolate_between`` needs of a frame, whichever partner, direction or early mode it is rendered with.  A
         name the store already holds raises; further frames may be recorded later under the same settings.  More than 8 frames
-        (``AID_KF_MAX_ROWS``, what one launch moves) are recorded in runs of up to 8.  Returns the decoded key frames."""
+        (``AID_KF_MAX_ROWS``, what one launch moves) are recorded in runs of up to 8.  ``guidance_rescale`` as in ``interpolate_single``: it
+        is part of what the frames are recorded under (a replay under another value raises).  Returns the decoded key frames."""
         names = [str(n) for n in names]
         k = len(names)
         lats = [latents[i:i + 1] for i in range(k)] if torch.is_tensor(latents) else list(latents)
@@ -697,9 +786,11 @@ class InterpolationStableDiffusionPipeline:
                 sl = slice(g0, g0 + KF_MAX_ROWS)
                 outs.append(self.record_keyframes(store, names[sl], lats[sl], None if prompts is None else prompts[sl],
                                                   None if embeds is None else embeds[sl], negative_prompt, num_inference_steps,
-                                                  warmup_ratio, aid_steps, guidance_scale, use_graphs, cross_attention_kwargs, output_type))
+                                                  warmup_ratio, aid_steps, guidance_scale, use_graphs, cross_attention_kwargs, output_type,
+                                                  guidance_rescale=guidance_rescale))
             return torch.cat(outs) if torch.is_tensor(outs[0]) else np.concatenate(outs)
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
+        gr = _check_rescale(guidance_rescale)
         dev, dtype = self._unet_device_dtype()
         cak = cross_attention_kwargs
         ls = cak.get("scale", None) if cak is not None else None
@@ -715,7 +806,7 @@ class InterpolationStableDiffusionPipeline:
         if not 1 <= n_aid <= num_inference_steps:
             raise ValueError(f"aid_steps must be in 1 .. num_inference_steps ({num_inference_steps}); got {n_aid}")
         settings = run_settings(num_inference_steps=num_inference_steps, guidance_scale=gs, dtype=dtype,
-                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls)
+                                timesteps=self.scheduler.timesteps, unet=self.unet, lora_scale=ls, guidance_rescale=gr)
         installed = dict(self.unet.attn_processors)          # restored at the end, as interpolate does
         store.begin_record(names, settings, n_aid, dev)
         try:
@@ -748,7 +839,7 @@ class InterpolationStableDiffusionPipeline:
                 noise_text = graphs.run(("cond", rec), cond_pass, x=x, t=td)
                 set_keyframe_store(self.unet, None)
                 noise_unc = graphs.run(("uncond",), uncond_pass, x=x, t=td)
-                noise = noise_unc + gs * (noise_text - noise_unc)
+                noise = _guided_noise(noise_text, noise_unc, gs, gr)
                 lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
             store.finish_record(lat0, embs, lat)
         finally:
@@ -763,23 +854,28 @@ class InterpolationStableDiffusionPipeline:
                             alpha: Optional[float] = None, beta: Optional[float] = None, batched_cfg: bool = True,
                             output_type: str = "np", use_graphs: Optional[bool] = None,
                             num_inference_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
-                            cross_attention_kwargs: Optional[Dict[str, Any]] = None):
+                            cross_attention_kwargs: Optional[Dict[str, Any]] = None, guidance_rescale: float = 0.0):
         """Render ``size`` frames from key frame ``a`` to key frame ``b`` of ``store``: the ``size - 2`` interior frames go through the
         UNet exactly as in an ``interpolate(..., endpoints=<recorded store>)`` replay — latents and embeddings of the two frames come
         from the store, their AID steps attend to the frames' recorded keys / values — and the two end frames are the stored final
         latents.  ``(b, a)`` renders the reverse direction from the same recordings; any ``early`` mode does.  ``num_inference_steps``
-        / ``guidance_scale`` default to the store's.  An unknown name raises ``KeyError``; a run that needs more AID steps than were
+        / ``guidance_scale`` default to the store's; ``guidance_rescale`` must be the recording's (a store recorded under a non-zero
+        rescale keeps the pair ``(guidance_scale, guidance_rescale)`` in its ``guidance_scale`` setting).  An unknown name raises ``KeyError``; a run that needs more AID steps than were
         recorded, or whose step count, guidance scale, dtype, timesteps, UNet or LoRA state differ from the recording's, raises
         ``ValueError`` naming what differs."""
         fa, fb = store[a], store[b]
         pair = store.between(a, b)
         steps = store.settings["num_inference_steps"] if num_inference_steps is None else num_inference_steps
-        gs = store.settings["guidance_scale"] if guidance_scale is None else guidance_scale
+        if guidance_scale is None:
+            gs = store.settings["guidance_scale"]
+            gs = gs[0] if isinstance(gs, tuple) else gs
+        else:
+            gs = guidance_scale
         return self.interpolate(fa.latent, fb.latent, guide_prompt=guide_prompt, negative_prompt=negative_prompt, size=size,
                                 num_inference_steps=steps, warmup_ratio=warmup_ratio, early=early, late=late, alpha=alpha, beta=beta,
                                 guidance_scale=gs, embeds_start=fa.embeds, embeds_end=fb.embeds, embeds_guide=embeds_guide,
                                 batched_cfg=batched_cfg, output_type=output_type, coef=coef, use_graphs=use_graphs,
-                                cross_attention_kwargs=cross_attention_kwargs, endpoints=pair)
+                                cross_attention_kwargs=cross_attention_kwargs, endpoints=pair, guidance_rescale=guidance_rescale)
 
     def interpolate_chain(self, store: KeyframeStore, names: Sequence[str], size: int = 7, **kwargs):
         """``interpolate_between`` for every consecutive pair of ``names``, in order, joined with each shared key frame once:

@@ -168,6 +168,27 @@ int aid_dora_gain(const void* w, const void* a_pack, const void* b_pack, const v
                   int32_t n_in, int32_t ldw, int32_t rank, int32_t dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Classifier-free guidance with the guidance rescale of arXiv 2305.08891 §3.4 — the combine the reference's loop runs between
+ * its two UNet passes and scheduler.step (pipeline_interpolated_sd.py:92-108, 1892-1902) — in one launch.  Per sample i of n,
+ * over the e elements of the sample, all arithmetic in fp32:
+ *   c   = u + guidance_scale * (t - u)                        t = text[i], u = uncond[i]
+ *   s_t = std(t), s_c = std(c)                                unbiased (e - 1), two-pass
+ *   out = c * (guidance_rescale * s_t / s_c + (1 - guidance_rescale))          one rounding to the storage dtype
+ * guidance_rescale 0 gives the plain combine c.  text / uncond / out [n, e] in the storage dtype (f16 / bf16 / f32), sample i
+ * at base + i * stride ELEMENTS, the e elements of a sample contiguous: the two halves of a batched [2 n, e] UNet output are two
+ * pointers into one tensor.  out may BE text or uncond (same base and stride); any other overlap of out with an input is refused.
+ * One workgroup per sample; 16-byte loads and stores for every sample whose three bases are 16-byte aligned, scalar otherwise
+ * and for the last e % 8 (f32: e % 4) elements.  s_c == 0 gives Inf / NaN, as the reference's division does.
+ * AID_ERR_ARG: a NULL pointer, n < 0, a stride < e, guidance_rescale outside [0, 1], partial overlap of out with an input;
+ * AID_ERR_SHAPE: e < 2, a pointer not aligned to the element size; AID_ERR_DTYPE; AID_ERR_NO_DEVICE.  n == 0 launches nothing.
+ * Reads exactly the n * e elements of text and of uncond, writes exactly the n * e elements of out.  One launch, no allocation,
+ * no synchronisation; capturable.
+ * ------------------------------------------------------------------------------------- */
+int aid_cfg_rescale(const void* text, const void* uncond, void* out, int32_t n, int64_t e, int64_t text_stride,
+                    int64_t uncond_stride, int64_t out_stride, float guidance_scale, float guidance_rescale, int32_t dtype,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * LayerNorm over the last dimension: y[r, :] = (x[r, :] - mean_r) * rsqrt(var_r + eps) * gamma + beta
  * — the norm1 / norm2 in front of the attention call in diffusers' BasicTransformerBlock (the step
  * before the path).  fp32 statistics, one rounding; gamma / beta may be NULL.
