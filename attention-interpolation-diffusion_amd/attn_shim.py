@@ -48,6 +48,13 @@ class AttnShim(nn.Module):
         self.upcast_softmax = False
         self.processor = processor
 
+    def __setattr__(self, name, value):
+        # a processor that is a plain object may replace one that is an nn.Module (diffusers' Attention.set_processor pops the
+        # registered module the same way): restoring the processors installed before an N-frame run needs it
+        if name == "processor" and not isinstance(value, nn.Module) and "processor" in self.__dict__.get("_modules", ()):
+            del self._modules["processor"]
+        super().__setattr__(name, value)
+
     # -- the helpers the reference processors call ---------------------------
     def prepare_attention_mask(self, attention_mask, target_length, batch_size, out_dim=3):
         """diffusers' ``Attention.prepare_attention_mask`` (third-party, restated from diffusers 0.27 - 0.31; not in SURVEY.md App. A,

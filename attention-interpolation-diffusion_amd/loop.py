@@ -22,31 +22,73 @@ from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
-from .processors import (HipAttnProcessor, InnerInterpolatedAttnProcessor, InterpolatedAttnProcessor,
-                         OuterInterpolatedAttnProcessor, cache_generation, clear_weight_caches)
+from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
+                         InnerInterpolatedIPAttnProcessor, InterpolatedAttnProcessor, OuterInterpolatedAttnProcessor,
+                         OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, cache_generation, clear_weight_caches)
 
 EARLY_MODES = ("pure_inner", "fused_inner", "pure_outer", "fused_outer")
 
 
+IP_VARIANTS = ("interpolate", "scale_control")
+
+
+def _adapter_of(cur):
+    """The IP-Adapter state (``to_k_ip`` / ``to_v_ip`` / ``scale`` / ``num_tokens``) behind an installed processor — the processor
+    itself or the ``ip_attn`` of an IP AID processor — or None for a layer without an adapter."""
+    for holder in (cur, getattr(cur, "ip_attn", None)):
+        if holder is not None and hasattr(holder, "to_k_ip"):
+            return holder
+    return None
+
+
 def install_sequence_processors(unet, size: int, early: str = "fused_outer", alpha: Optional[float] = None,
                                 beta: Optional[float] = None, num_inference_steps: int = 50,
-                                coef: Optional[torch.Tensor] = None) -> None:
+                                coef: Optional[torch.Tensor] = None, ip_adapter: Optional[str] = None) -> None:
     """One AID processor per attention layer for an N-frame sequence; Beta(alpha, beta) coefficients with
     alpha = beta = num_inference_steps by default (gradio_src/...stable_diffusion.py:203-206, 237-260).
     ``coef`` overrides the schedule (used by the frame-sharded layout: the local rows of the global
-    schedule)."""
+    schedule).
+    ``ip_adapter`` (None = text processors on every layer): the layers that hold an IP-Adapter — their installed processor, or its
+    ``ip_attn``, has ``to_k_ip`` — get the IP variant instead: "interpolate" = ``OuterInterpolatedIPAttnProcessor`` for an outer
+    ``early`` (``is_fused`` from ``early``) / ``InnerInterpolatedIPAttnProcessor`` for ``fused_inner`` (``pure_inner`` raises what the
+    processor raises), "scale_control" = ``ScaleControlIPAttnProcessor`` (an outer ``early``).  Their ``ip_attn`` is the layer's
+    ``HipIPAdapterAttnProcessor`` — the installed one, or one sharing the installed adapter's weights and scale list; a foreign
+    processor kept by ``load_aid_ip_adapter(keep_original=True)`` stays.  Every other layer gets the text processor as without
+    ``ip_adapter``.  A UNet without any adapter layer raises ``ValueError``."""
     if early not in EARLY_MODES:
         raise ValueError(f"early must be one of {EARLY_MODES}")
+    if ip_adapter is not None:
+        if ip_adapter not in IP_VARIANTS:
+            raise ValueError(f"ip_adapter must be one of {IP_VARIANTS} or None, got {ip_adapter!r}")
+        if ip_adapter == "scale_control" and not early.endswith("outer"):
+            raise ValueError(f"scale control (only `image_end`) interpolates the text attention outer: early must be 'pure_outer' or "
+                             f"'fused_outer', got {early!r}")
+        if ip_adapter == "interpolate" and early == "pure_inner":
+            raise RuntimeError("InnerInterpolatedIPAttnProcessor needs is_fused=True when image embeddings are "
+                               "passed: the reference's image branch multiplies un-split keys "
+                               "(batch1 dim mismatch in bmm, interpolation.py:525)")
+        if not any(_adapter_of(cur) is not None for cur in unet.attn_processors.values()):
+            raise ValueError("image inputs need a loaded IP-Adapter: no attention layer of the UNet holds one (load_ip_adapter / "
+                             "load_aid_ip_adapter first)")
     alpha = num_inference_steps if alpha is None else alpha
     beta = num_inference_steps if beta is None else beta
     cls = OuterInterpolatedAttnProcessor if early.endswith("outer") else InnerInterpolatedAttnProcessor
+    ip_cls = ScaleControlIPAttnProcessor if ip_adapter == "scale_control" else \
+        OuterInterpolatedIPAttnProcessor if early.endswith("outer") else InnerInterpolatedIPAttnProcessor
+    current = dict(unet.attn_processors)
     clear_weight_caches()                    # (see processors.py: in-place weight edits are invisible to the cache keys)
     procs = {}
-    for name in unet.attn_processors.keys():
+    for name, cur in current.items():
         # (a given schedule may hold ONE coefficient — the interior frame of an end-point-store replay; the Beta schedule it
         #  replaces needs two points)
-        p = cls(size=size if coef is None else max(size, 2), is_fused=early.startswith("fused"), alpha=alpha, beta=beta,
-                original_attn=HipAttnProcessor())
+        kw = dict(size=size if coef is None else max(size, 2), is_fused=early.startswith("fused"), alpha=alpha, beta=beta)
+        adapter = _adapter_of(cur) if ip_adapter is not None else None
+        if adapter is not None:
+            if not isinstance(adapter, HipIPAdapterAttnProcessor) and (adapter is cur or getattr(adapter, "weights_only", False)):
+                adapter = HipIPAdapterAttnProcessor.wrap(adapter)
+            p = ip_cls(ip_attn=adapter, **kw)
+        else:
+            p = cls(original_attn=HipAttnProcessor(), **kw)
         if coef is not None:
             assert coef.numel() == size
             p.size = size

@@ -620,7 +620,8 @@ class InterpolationStableDiffusionPipeline:
                     embeds_start=None, embeds_end=None, embeds_guide=None, batched_cfg: bool = True,
                     output_type: str = "np", coef: Optional[Sequence[float]] = None, use_graphs: Optional[bool] = None,
                     cross_attention_kwargs: Optional[Dict[str, Any]] = None, endpoints: Optional[EndpointStore] = None,
-                    guidance_rescale: float = 0.0):
+                    guidance_rescale: float = 0.0, image_start=None, image_end=None, image_embeds_start=None,
+                    image_embeds_end=None, init: str = "linear"):
         """gradio_src/pipeline_interpolated_stable_diffusion.py:163-304 with the root pipelines' warm-up count
         (``i < int(T * warmup_ratio)`` with 0-based ``i``).  ``late`` must be "self" (plain
         attention) or one of the AID modes.  ``batched_cfg``: the two passes of a step run as one UNet call.
@@ -630,9 +631,26 @@ class InterpolationStableDiffusionPipeline:
         ``use_graphs``, ``cross_attention_kwargs`` and ``endpoints`` as in ``interpolate_single`` (a replay renders the ``size - 2``
         interior frames; a store recorded by either method replays in the other); ``guidance_rescale`` (build-specific here) as in
         ``interpolate_single``.  The processors ``load_aid`` / ``load_aid_ip_adapter`` installed are put
-        back when the run ends (the run works with its own N-frame processors)."""
+        back when the run ends (the run works with its own N-frame processors).
+        ``image_start`` / ``image_end`` / ``image_embeds_start`` / ``image_embeds_end`` / ``init`` (build-specific here) as in
+        ``interpolate_single``, for a UNet whose IP-Adapter is loaded: frame k attends with ``mix(start, end, t_k)`` of the positive
+        (conditional pass) and of the negative (unconditional pass) image embeddings, ``t_k`` its coefficient and ``mix`` ``torch.lerp``
+        for ``init == "linear"``, else ``slerp``; only ``image_end`` = scale control.  The adapter layers then run the IP processor
+        ``early`` / ``late`` name (``install_sequence_processors(ip_adapter=)``), every other layer the text processors.  With several
+        adapters, ``ip_adapter_masks`` or a foreign processor kept by ``load_aid_ip_adapter(keep_original=True)`` the two passes of a step
+        run as two UNet calls whatever ``batched_cfg`` says.  ``endpoints`` with images raises."""
         if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
             raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
+        if (image_start is not None and image_end is None) or \
+                (image_embeds_start is not None and image_end is None and image_embeds_end is None):   # pipeline_interpolated_sd.py:1608-1612
+            raise ValueError("Please provide both `image_start` and `image_end` to interpolate, or only `image_end` to "
+                             "control the scale.")
+        if (image_start is not None or image_end is not None) and self._encode_image is None:
+            raise ValueError("image inputs need an `encode_image` component; pass image_embeds_start / image_embeds_end")
+        with_images = image_end is not None or image_embeds_end is not None
+        if with_images and endpoints is not None:
+            raise NotImplementedError("an end-point store with IP-Adapter image inputs: the store holds the text processors' "
+                                      "self-attention keys / values only")
         gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
         gr = _check_rescale(guidance_rescale)
         dev, dtype = self._unet_device_dtype()
@@ -660,6 +678,10 @@ class InterpolationStableDiffusionPipeline:
                 batch.uncond = linear_interpolation(unc_s[0], unc_e[0], ts=ts)
                 if pooled is not None:
                     pooled = (linear_interpolation(cond_s[1], cond_e[1], ts=ts), linear_interpolation(unc_s[1], unc_e[1], ts=ts))
+        img = self._image_embeds_sequence(image_start, image_end, image_embeds_start, image_embeds_end, batch.coef, init, dev, dtype) \
+            if with_images else None
+        ip_variant = None if img is None else \
+            ("interpolate" if image_start is not None or image_embeds_start is not None else "scale_control")
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         warmup_steps = int(num_inference_steps * warmup_ratio)
         installed = dict(self.unet.attn_processors)          # what load_aid / load_aid_ip_adapter put there: restored at the end
@@ -698,19 +720,30 @@ class InterpolationStableDiffusionPipeline:
             procs = {}
             for mode in {early} | ({late} - {"self"}):
                 install_sequence_processors(self.unet, size, early=mode, alpha=alpha, beta=beta,
-                                            num_inference_steps=num_inference_steps, coef=run_coef)
+                                            num_inference_steps=num_inference_steps, coef=run_coef, ip_adapter=ip_variant)
                 if isinstance(endpoints, KeyframePair):      # (interpolate_between: the pair's two frames of a KeyframeStore)
                     set_keyframe_store(self.unet, endpoints.store, between=(endpoints.a, endpoints.b), endpoint_ctx=ectx)
                 elif ep_mode is not None:
                     set_endpoint_store(self.unet, endpoints, endpoint_ctx=ectx)
                 procs[mode] = dict(self.unet.attn_processors)
+            if img is not None and batched_cfg:
+                # riders stand for the de-activated pass of ONE unmasked adapter on the package's own processor; elsewhere (several
+                # adapters, ip_adapter_masks, a kept foreign processor) the two passes run as two UNet calls — the same result
+                masks = None if cak is None else cak.get("ip_adapter_masks")
+                batched_cfg = all(p_.riders_supported(masks) for ps in procs.values() for p_ in ps.values()
+                                  if isinstance(p_, P._IPBase))
             graphs = _PassGraphs(_use_graphs(use_graphs, dev))
             ctx_both = torch.cat([cond, unc]) if batched_cfg else None      # ONE tensor for the whole run: the text K / V cache keys on it
             if batched_cfg:
-                added_both = self._added_cond(None if pooled is None else torch.cat(pooled), 2 * size)
-            else:
+                added_both = self._added_cond(None if pooled is None else torch.cat(pooled), 2 * size) if img is None else \
+                    self._added_cond(None if pooled is None else torch.cat(pooled), 2 * size,
+                                     [torch.cat([p_, n_]) for p_, n_ in zip(*img)])      # image rows [cond frames ; uncond frames]
+            elif img is None:
                 added_c = self._added_cond(None if pooled is None else pooled[0], size)
                 added_u = self._added_cond(None if pooled is None else pooled[1], size)
+            else:
+                added_c = self._added_cond(None if pooled is None else pooled[0], size, img[0])
+                added_u = self._added_cond(None if pooled is None else pooled[1], size, img[1])
 
             def both_pass(x, t):
                 return self._unet(torch.cat([x, x]), t, ctx_both, added_both, cak)
@@ -730,7 +763,8 @@ class InterpolationStableDiffusionPipeline:
                     endpoints.set_step(i)
                 gkey = (mode,) if ep_mode is None else (mode, ep_mode)
                 if batched_cfg:
-                    set_aid_active(self.unet, mode != "self", plain_tail=size if mode != "self" else 0)
+                    # (the IP processors that compute de-activated themselves — scale control — need to know their riders there too)
+                    set_aid_active(self.unet, mode != "self", plain_tail=size if mode != "self" or img is not None else 0)
                     set_ctx_index(self.unet, None if idx is None else idx + [j + n_distinct for j in idx])
                     both = graphs.run(("both",) + gkey, both_pass, x=x, t=td)
                     noise_text, noise_unc = both[:size], both[size:]
@@ -930,6 +964,25 @@ class InterpolationStableDiffusionPipeline:
         pos = torch.cat([pos_s, mix(pos_s, pos_e), pos_e], dim=0)
         neg = torch.cat([neg_s, mix(neg_s, neg_e), neg_e], dim=0)
         return [pos], [neg]
+
+    def _image_embeds_sequence(self, image_start, image_end, ies, iee, coef, init, dev, dtype):
+        """``_image_embeds_single`` evaluated at every coefficient of an N-frame run, one row per frame: ``([pos], [neg])`` with
+        ``pos`` = ``[pos_start, mix(pos_start, pos_end, t_1), ..., pos_end]`` for the conditional pass and ``neg`` likewise for the
+        unconditional one (one list entry per adapter: a pair may hold lists of tensors); only the end image given = scale control
+        (the start rows are the NEGATIVE embeddings of the end image)."""
+        if image_end is not None and iee is None:
+            iee = self._encode_image(image_end)
+        if image_start is not None and ies is None:
+            ies = self._encode_image(image_start)
+        as_list = (lambda e: [t_.to(dev, dtype) for t_ in (e if isinstance(e, (list, tuple)) else [e])])
+        neg_e, pos_e = as_list(iee[0]), as_list(iee[1])
+        neg_s, pos_s = (neg_e, neg_e) if ies is None else (as_list(ies[0]), as_list(ies[1]))
+        ts = [float(t) for t in coef.tolist()]
+        mix = (lambda a, b, t: torch.lerp(a, b, t)) if init == "linear" else (lambda a, b, t: slerp(a, b, t))
+
+        def frames(a, b):
+            return torch.cat([a] + [mix(a, b, t) for t in ts[1:-1]] + [b], dim=0).contiguous()
+        return [frames(a, b) for a, b in zip(pos_s, pos_e)], [frames(a, b) for a, b in zip(neg_s, neg_e)]
 
     def _unet_device_dtype(self):
         p = next(self.unet.parameters())

@@ -295,7 +295,10 @@ class BetaPriorPipeline:
                                                latent_end=latent_end, num_inference_steps=num_inference_steps, **kw)
             frames = out["images"] if isinstance(out, dict) else out.images
         else:
-            # the N-frame run renders with the mode load_aid / load_aid_ip_adapter selected (the batch-3 call above does too)
+            # the N-frame run renders with the mode load_aid / load_aid_ip_adapter selected (the batch-3 call above does too).  Image
+            # prompts (image_start / image_end / image_embeds_start / image_embeds_end / init in ``kw``) go to ``interpolate`` as they go
+            # to ``interpolate_single``: each frame attends with the image embeddings mixed at its coefficient; "scale_control" is
+            # only ``image_end`` over the outer text interpolation
             early = getattr(self.pipe, "_aid_early", None)
             if early not in ("pure_inner", "fused_inner", "pure_outer", "fused_outer"):
                 early = "fused_outer"

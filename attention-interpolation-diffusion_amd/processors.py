@@ -17,7 +17,8 @@ Differences from the reference that are deliberate and documented:
   * the per-call host->device copy of ``coef`` (interpolation.py:663) is cached on the device;
   * optional ``ctx_index`` (attribute or keyword of ``__call__``, e.g. through ``cross_attention_kwargs``): frames
     that share a text context (PAID guide prompt) have its keys / values projected once.  Results are bit-identical
-    to passing the repeated contexts.
+    to passing the repeated contexts.  The IP-Adapter variants take it too, and ``plain_tail`` rider frames (the unconditional half
+    of a batched classifier-free-guidance call) like the text processors.
 """
 from __future__ import annotations
 
@@ -864,6 +865,12 @@ class HipIPAdapterAttnProcessor(nn.Module):
 
 
 class _IPBase(InterpolatedAttnProcessor):
+    """Shared by the three IP variants.  Build-specific beside the reference's surface, as on the text processors:
+    ``plain_tail`` rider frames behind the ``coef.numel()`` interpolated ones (the unconditional half of a batched
+    classifier-free-guidance call: plain text attention on their own context plus ``scale[0]`` x plain attention on their own image
+    rows — what the de-activated :class:`HipIPAdapterAttnProcessor` computes for one unmasked adapter; the image-embedding rows are
+    ``[cond frames ; rider frames]``), and ``ctx_index`` (attribute or keyword) for frames that share a text context."""
+
     def __init__(self, t=None, size=7, is_fused=False, alpha=1, beta=1, ip_attn=None):
         super().__init__(t=t, size=size, is_fused=is_fused, alpha=alpha, beta=beta)
         self.num_tokens = ip_attn.num_tokens if hasattr(ip_attn, "num_tokens") else (16,)
@@ -872,24 +879,43 @@ class _IPBase(InterpolatedAttnProcessor):
 
     def fused_sublayer(self, attn, norm, hidden_states, encoder_hidden_states=None, ctx_index=None):
         """``h + attn(norm(h), ctx)`` as three steps (the one-call form covers the text processors only)."""
-        return hidden_states + self(attn, norm(hidden_states), encoder_hidden_states)
+        return hidden_states + self(attn, norm(hidden_states), encoder_hidden_states, ctx_index=ctx_index)
 
-    def _fallback(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb):
+    def riders_supported(self, ip_adapter_masks=None, attention_mask=None) -> bool:
+        """Whether PLAIN rider frames of ONE call reproduce what the de-activated pass computes at this layer: one unmasked adapter on
+        this package's own processor.  Several adapters, ``ip_adapter_masks``, an ``attention_mask`` or a foreign ``ip_attn``
+        (``keep_original=True``) do not: run the conditional and the unconditional pass as two calls there."""
+        if ip_adapter_masks is not None or attention_mask is not None:
+            return False
+        ip_attn = self.ip_attn
+        if hasattr(ip_attn, "to_k_ip"):
+            own = isinstance(ip_attn, HipIPAdapterAttnProcessor) or getattr(ip_attn, "weights_only", False)
+            return bool(own) and len(ip_attn.to_k_ip) == 1
+        return ip_attn is None or isinstance(ip_attn, HipAttnProcessor)
+
+    def _fallback(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index=None, ip_adapter_masks=None):
         """De-activated: the wrapped processor, like the reference (interpolation.py:248-251).  A wrapped object that
-        cannot be called (a bare weight holder) runs the HIP IP-Adapter attention on its weights instead."""
+        cannot be called (a bare weight holder) runs the HIP IP-Adapter attention on its weights instead.  The wrapped processors
+        know no frame -> context map: distinct contexts are repeated per frame first (the same numbers)."""
+        if ctx_index is not None and encoder_hidden_states is not None:
+            encoder_hidden_states = _per_frame_context(encoder_hidden_states, ctx_index, hidden_states.shape[0])
+        kw = {} if ip_adapter_masks is None else dict(ip_adapter_masks=ip_adapter_masks)
         if callable(self.ip_attn) and not getattr(self.ip_attn, "weights_only", False):
-            return self.ip_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+            if kw and not isinstance(self.ip_attn, HipIPAdapterAttnProcessor) and not hasattr(self.ip_attn, "to_k_ip"):
+                kw = {}                                  # (a plain text layer takes no image masks)
+            return self.ip_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb, **kw)
         if hasattr(self.ip_attn, "to_k_ip"):
             return HipIPAdapterAttnProcessor.wrap(self.ip_attn)(attn, hidden_states, encoder_hidden_states,
-                                                                attention_mask, temb)
+                                                                attention_mask, temb, **kw)
         return HipAttnProcessor()(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
 
     def _frames(self, x) -> int:
         n = self.coef.numel()
-        if x.shape[0] != n:
+        if x.shape[0] != n + self.plain_tail:
             raise RuntimeError(f"the IP processors run a batch of coef.numel() = {n} frames "
-                               f"[start, ..., end] (the reference hard-wires 3, interpolation.py:300-303); "
-                               f"got a batch of {x.shape[0]}")
+                               f"[start, ..., end] (the reference hard-wires 3, interpolation.py:300-303)"
+                               + (f" and plain_tail = {self.plain_tail} rider frames behind them" if self.plain_tail else "")
+                               + f"; got a batch of {x.shape[0]}")
         return n
 
     def _image_rows(self, ip, n: int, which: str):
@@ -907,9 +933,16 @@ class _IPBase(InterpolatedAttnProcessor):
         last = rows[r * (n - 1): r * (n - 1) + 1]
         return last, _zeros_map(self._ctx_cache, n, rows.device)
 
-    def _call(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, mode, branch_of):
+    def _call(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, mode, branch_of, ctx_index=None,
+              ip_adapter_masks=None):
         text, ip = _split_ip(encoder_hidden_states, self.num_tokens)
         residual, x, text, shape4, mask = _prologue(attn, hidden_states, text, attention_mask, temb)
+        tail = self.plain_tail
+        if tail and not self.riders_supported(ip_adapter_masks, attention_mask):
+            raise RuntimeError("plain_tail rider frames on an IP-Adapter processor stand for the de-activated pass of ONE unmasked "
+                               "adapter on the HIP processors; with several adapters, ip_adapter_masks, an attention_mask or a foreign "
+                               "ip_attn (keep_original=True) run the conditional and the unconditional pass as two calls "
+                               "(plain_tail = 0; interpolate(batched_cfg=True) does so by itself)")
         if mask is not None:
             # the reference hands the text-length mask to the IMAGE attention too (interpolation.py:141-143, 191-193, 352-359,
             # 525): T image tokens against an L-wide mask fails at the broadcast unless T == L, and fused text keys fail first
@@ -923,16 +956,39 @@ class _IPBase(InterpolatedAttnProcessor):
             raise NotImplementedError("a key-frame store on an IP-Adapter processor: the image branch attends to the end points' image "
                                       "keys, which the store does not hold (text processors only)")
         n = self._frames(x)
+        nb = n + tail
         wq, wk, wv, wo, bo = _weights(attn)
-        coef, vals = self._coef_state(x.device, x.dtype, x.shape[0])
+        coef, vals = self._coef_state(x.device, x.dtype, nb)
         fused = self.is_fused if mode != "plain" else False
-        branch = branch_of(ip, n, coef) if ip is not None else None
+        begin, end = 0, n - 1
+        ctx_map = idx = None
+        ctx_index = self.ctx_index if ctx_index is None else ctx_index
+        if text is not None and ctx_index is not None:
+            text, ctx_map, idx = _shared_context(self._ctx_cache, ctx_index, text, nb)
+            begin, end = idx[0], idx[n - 1]              # end-point rows of the key / value tensors
+        elif text is not None:
+            text = text.contiguous()
+        branch = branch_of(ip, n, coef, tail) if ip is not None else None
         _no_ip_lora(self.ip_attn)
-        y = ops.processor_fwd(x, None if text is None else text.contiguous(), wq, wk, wv, wo, bo, attn.heads,
-                              mode=mode, fused=fused, coef=coef, begin=0, end=n - 1, ip=branch,
-                              seg_executed=ops.executed_segments(mode, fused, vals, n, None, 0, n - 1),
+        y = ops.processor_fwd(x, text, wq, wk, wv, wo, bo, attn.heads,
+                              mode=mode, fused=fused, coef=coef, begin=begin, end=end, ctx_map=ctx_map, ip=branch,
+                              n_plain=tail if mode != "plain" else 0,
+                              seg_executed=ops.executed_segments(mode, fused, vals, nb, idx, begin, end),
                               lora=lora.args(attn, x.dtype, x.device, text is not None))
         return _epilogue(attn, y, residual, shape4)
+
+
+def _per_frame_context(encoder_hidden_states, ctx_index, batch: int):
+    """``encoder_hidden_states`` (a tensor or a ``(text, [ip])`` tuple) with the distinct text contexts of a frame -> context map
+    repeated per frame — for a wrapped processor that knows no ``ctx_index``.  One context per frame already: unchanged."""
+    text = encoder_hidden_states[0] if isinstance(encoder_hidden_states, tuple) else encoder_hidden_states
+    if text is None or text.shape[0] == batch:
+        return encoder_hidden_states
+    idx = [int(i) for i in (ctx_index.tolist() if torch.is_tensor(ctx_index) else ctx_index)]
+    if len(idx) != batch or min(idx) < 0 or max(idx) >= text.shape[0]:
+        raise RuntimeError(f"ctx_index has {len(idx)} entries up to {max(idx)} for a batch of {batch} frames and {text.shape[0]} contexts")
+    text = text.index_select(0, torch.tensor(idx, dtype=torch.long, device=text.device))
+    return (text,) + tuple(encoder_hidden_states[1:]) if isinstance(encoder_hidden_states, tuple) else text
 
 
 def _no_ip_lora(ip_attn) -> None:
@@ -955,15 +1011,19 @@ class OuterInterpolatedIPAttnProcessor(_IPBase):
     r"""Outer interpolation combined with the IP-Adapter image attention (interpolation.py:214-387):
     O = (1-c) [A_text_begin + s A_ip_begin] + c [A_text_end + s A_ip_end]."""
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
+                 ctx_index=None, ip_adapter_masks=None):
+        ctx_index = self.ctx_index if ctx_index is None else ctx_index
         if not self.activated:
-            return self._fallback(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+            return self._fallback(attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index, ip_adapter_masks)
 
-        def branch(ip, n, coef):                                            # interpolation.py:329-367 (linear in O)
-            tokens, _ = self._image_rows(ip, n, "per_frame")
+        def branch(ip, n, coef, tail=0):                                    # interpolation.py:329-367 (linear in O)
+            # (riders: image rows [cond frames ; rider frames]; a rider's negative coefficient makes it attend PLAIN to its own row)
+            tokens, _ = self._image_rows(ip, n + tail, "per_frame")
             return dict(tokens=tokens, wk=self.ip_attn.to_k_ip[0].weight, wv=self.ip_attn.to_v_ip[0].weight,
                         mode="same", scale=float(self.scale[0]), begin=0, end=n - 1)
-        return self._call(attn, hidden_states, encoder_hidden_states, attention_mask, temb, "outer", branch)
+        return self._call(attn, hidden_states, encoder_hidden_states, attention_mask, temb, "outer", branch, ctx_index,
+                          ip_adapter_masks)
 
 
 class InnerInterpolatedIPAttnProcessor(_IPBase):
@@ -971,33 +1031,93 @@ class InnerInterpolatedIPAttnProcessor(_IPBase):
     As in the reference the image branch attends with each frame's OWN image keys and is only
     shape-valid with ``is_fused=True`` (interpolation.py:512-527)."""
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
+                 ctx_index=None, ip_adapter_masks=None):
+        ctx_index = self.ctx_index if ctx_index is None else ctx_index
         if not self.activated:
-            return self._fallback(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+            return self._fallback(attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index, ip_adapter_masks)
 
-        def branch(ip, n, coef):                                            # interpolation.py:502-505, 525-530
+        def branch(ip, n, coef, tail=0):                                    # interpolation.py:502-505, 525-530
             if not self.is_fused:
                 raise RuntimeError("InnerInterpolatedIPAttnProcessor needs is_fused=True when image embeddings are "
                                    "passed: the reference's image branch multiplies un-split keys "
                                    "(batch1 dim mismatch in bmm, interpolation.py:525)")
-            tokens, _ = self._image_rows(ip, n, "per_frame")
+            tokens, _ = self._image_rows(ip, n + tail, "per_frame")          # (riders attend to their own rows like every frame)
             return dict(tokens=tokens, wk=self.ip_attn.to_k_ip[0].weight, wv=self.ip_attn.to_v_ip[0].weight,
                         mode="plain", scale=float(self.scale[0]))
-        return self._call(attn, hidden_states, encoder_hidden_states, attention_mask, temb, "inner", branch)
+        return self._call(attn, hidden_states, encoder_hidden_states, attention_mask, temb, "inner", branch, ctx_index,
+                          ip_adapter_masks)
 
 
 class ScaleControlIPAttnProcessor(_IPBase):
     r"""Image-prompt scale control (interpolation.py:51-211): text attention is outer-interpolated
     (activated) or plain (de-activated); the image attention of the END frame's rows ([6:9]) is added with the
-    per-frame coefficient."""
+    per-frame coefficient.
+    With ``plain_tail`` riders (the unconditional half of a batched call, one rider per frame) the image rows are
+    ``[cond frames ; rider frames]``: the cond frames attend to the END cond frame's rows — the end image's positive embedding — and
+    the riders to the END rider's rows — its negative embedding —, each with its frame's coefficient, which is what this processor
+    computes de-activated on the unconditional batch.  The per-frame scales then live in a buffer of their own (the coefficient
+    buffer holds the riders' negative marks)."""
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
-        def branch(ip, n, coef):                                            # interpolation.py:137-150 / 187-196
-            tokens, row_map = self._image_rows(ip, n, "last")
-            return dict(tokens=tokens, wk=self.ip_attn.to_k_ip[0].weight, wv=self.ip_attn.to_v_ip[0].weight,
-                        mode="plain", scale=1.0, frame_scale=coef, map=row_map)
+    def __init__(self, t=None, size=7, is_fused=False, alpha=1, beta=1, ip_attn=None):
+        super().__init__(t=t, size=size, is_fused=is_fused, alpha=alpha, beta=beta, ip_attn=ip_attn)
+        self._scale_dev: Dict[Tuple, list] = {}          # (device, dtype, coefficients, riders) -> [tensor, values, coef._version]
+
+    @staticmethod
+    def _scale_values(coef: torch.Tensor, dtype: torch.dtype, tail: int) -> Tuple[float, ...]:
+        vals = _coef_values(coef, dtype, 0)
+        if tail != len(vals):
+            raise RuntimeError(f"ScaleControlIPAttnProcessor: plain_tail = {tail} riders for {len(vals)} frames — the riders are the "
+                               "unconditional twins of the frames, one each")
+        return vals + vals
+
+    def _frame_scale(self, device, dtype, tail: int) -> torch.Tensor:
+        """fp32 device [n + tail]: the cond frames' coefficients (rounded to the compute dtype like ``coef``), then the riders'.
+        Allocated once per layout and rewritten in place, like the coefficient buffers (captured graphs hold its address)."""
+        coef = self.coef
+        key = (device, dtype, coef.numel(), tail)
+        ent = self._scale_dev.get(key)
+        ver = _version_of(coef)
+        if ent is None:
+            vals = self._scale_values(coef, dtype, tail)
+            ent = self._scale_dev[key] = [torch.tensor(vals, dtype=torch.float32).to(device), vals, ver]
+        elif ver is None or ent[2] != ver:
+            _rewrite(ent, self._scale_values(coef, dtype, tail), ver)
+        return ent[0]
+
+    def _refresh_coef_buffers(self) -> None:
+        super()._refresh_coef_buffers()
+        coef = self._coef
+        for (device, dtype, n, tail), ent in getattr(self, "_scale_dev", {}).items():      # (not there yet while __init__ assigns coef)
+            if n == coef.numel():
+                _rewrite(ent, self._scale_values(coef, dtype, tail), _version_of(coef))
+
+    def _rider_map(self, n: int, tail: int, r: int, device) -> torch.Tensor:
+        """frame -> image row with riders: the END cond frame's row group for the cond frames, the END rider's for the riders (row j of
+        the group for frame j where a group has one row per frame, the reference's ``[6:9]``; else its first row)."""
+        key = ("ip_riders", n, tail, r, device)
+        hit = self._ctx_cache.get(key)
+        if hit is None:
+            rows = [r * (n - 1) + (i if r == n else 0) for i in range(n)] + \
+                   [r * (n + tail - 1) + (j if r == tail else 0) for j in range(tail)]
+            hit = self._ctx_cache[key] = torch.tensor(rows, dtype=torch.int32, device=device)
+        return hit
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
+                 ctx_index=None, ip_adapter_masks=None):
+        def branch(ip, n, coef, tail=0):                                    # interpolation.py:137-150 / 187-196
+            if not tail:
+                tokens, row_map = self._image_rows(ip, n, "last")
+                return dict(tokens=tokens, wk=self.ip_attn.to_k_ip[0].weight, wv=self.ip_attn.to_v_ip[0].weight,
+                            mode="plain", scale=1.0, frame_scale=coef, map=row_map)
+            rows = _ip_token_rows(ip)
+            if rows.shape[0] % (n + tail):
+                raise RuntimeError(f"{rows.shape[0]} image-embedding rows for {n} frames and {tail} riders")
+            return dict(tokens=rows, wk=self.ip_attn.to_k_ip[0].weight, wv=self.ip_attn.to_v_ip[0].weight,
+                        mode="plain", scale=1.0, frame_scale=self._frame_scale(rows.device, hidden_states.dtype, tail),
+                        map=self._rider_map(n, tail, rows.shape[0] // (n + tail), rows.device))
         return self._call(attn, hidden_states, encoder_hidden_states, attention_mask, temb,
-                          "outer" if self.activated else "plain", branch)
+                          "outer" if self.activated else "plain", branch, ctx_index, ip_adapter_masks)
 
 
 # ---------------------------------------------------------------------------------------------
