@@ -317,8 +317,9 @@ class AttnCall:
         return K2, VT2
 
     def run(self, mode, fused, coef=None, begin=0, end=-1, kv_map=None, frame_scale=None, out_scale=1.0, accumulate=False,
-            base=None, bias=None, k2=None, vt2=None):
-        """One aid_attn_fwd through the C ABI; returns (variant, out Guarded, fp64 expected [n, s, c])."""
+            base=None, bias=None, k2=None, vt2=None, f32_split=0):
+        """One aid_attn_fwd through the C ABI; returns (variant, out Guarded, fp64 expected [n, s, c]).  ``f32_split`` = 1 (float32
+        only): permit the three-term bf16 split (AidAttnArgs.f32_split)."""
         n, s, c, l = self.n, self.s, self.c, self.l
         end = end % self.n_kv
         Og = self.out_buffer()
@@ -340,6 +341,8 @@ class AttnCall:
         a.accumulate, a.dtype = int(accumulate), ops._dtype_code(self.Q.view)
         a.softmax_scale, a.out_scale = float(self.d ** -0.5), float(out_scale)
         a.n_plain = 0 if coef is None else int(sum(1 for x in coef if x < 0))
+        if f32_split:
+            a.f32_split = int(f32_split)
         bias64 = None
         if bias is not None:
             a.bias, a.bias_fs, a.bias_hs, a.bias_rs = bias.ptr, bias.fs, 0, bias.ld
