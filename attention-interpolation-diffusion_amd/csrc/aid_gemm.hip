@@ -5,7 +5,7 @@
 // gfx950 mapping: BM x BN block tile, waves in a WM x WN grid, each wave owns MB x NB MFMA 32x32x16
 // blocks.  The MFMA is issued "transposed" (D rows = n, cols = m) so every lane ends up with 4
 // consecutive n of one output row.  The 1-D grid is remapped XCD-aware so the blocks that share an A
-// row panel run on one XCD / one L2.
+// row panel run on one XCD / one L2.  (The 288-row engine issues the same products as MFMA 16x16x32: struct PingPongX.)
 //
 //  * aid_gemm_nt_pipe_kernel — lock-step engine, 128 x 128 x 64 tiles, 2 workgroups / CU (every k % 64 == 0 shape
 //    can run on it).  Operand tiles go HBM -> LDS directly (global_load_lds_dwordx4, 1 KiB per wave-instruction,
@@ -1036,6 +1036,25 @@ static_assert(Engine<bf16, 128, 128, 64, PP_SMALL_NS, 2, 4>::SMEM <= PingPong<bf
 // reads per K tile and wave (rows 256 .. 287, read by everybody), 4 more MFMAs (spread over phase 1, one per four main
 // MFMAs: the chain on the ninth accumulator never stalls) and 16 more accumulator registers (144 + 80 fragments).
 // LDS: each parity grows by the strip's 32 rows x 128 B (4 DMA pieces per K tile, issued by waves 0 - 3 with the A halves).
+//
+// Product shape: v_mfma_f32_16x16x32 (this engine only; every other engine issues 32x32x16).  The loop is power-bound on real
+// operands, not issue-bound: both shapes need the same cycles per flop, but on N(0, 1) operands the chip
+// holds a higher clock under the 16x16x32 stream — LDS-fed bare loops at this engine's ratio of reads to MFMAs: 1.11 x the TFLOP/s
+// in bf16, 1.12 x in f16 (tools/ubench/mfma_shape.hip, profiles/mfma_shape.txt); on zeros the shapes tie.  Same LDS image, DMA
+// stream, waits and barriers as before; a fragment is 16 rows x 32 k (still 16 B per lane: lane (l15, kg) reads chunk
+// (4 j + kg) ^ swz(row) of row base + l15, conflict-free under the ds_read_b128 lane groups), a phase is 32 MFMAs on sixteen
+// 16 x 16 blocks instead of 16 on four 32 x 32 blocks, the strip 8 per K tile on four blocks; fragment and accumulator registers
+// are unchanged (80 + 144).  Every block sums k in the same order as before, and the results are bit-identical to the 32x32x16
+// loop's on every shape measured (profiles/ppx_mfma16_ab.txt).
+// D(16x16, fp32) += A(16x32) * B(32x16).  Lane l supplies A[i = l&15][8*(l>>4) .. +7] and B[8*(l>>4) .. +7][j = l&15]; lane l
+// receives D[4*(l>>4) + r][l&15], r in [0,4).
+__device__ __forceinline__ f32x4 mfma16(const Vec<f16>::v8& a, const Vec<f16>::v8& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma16(const Vec<bf16>::v8& a, const Vec<bf16>::v8& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
 template <typename T>
 struct PingPongX : PingPong<T> {
     typedef PingPong<T> PP;
@@ -1051,13 +1070,22 @@ struct PingPongX : PingPong<T> {
     using PP::smem; using PP::tid; using PP::lane; using PP::wave; using PP::wm; using PP::wn; using PP::wr;
     using PP::l31; using PP::hi; using PP::aoff; using PP::boff; using PP::ax; using PP::bx; using PP::acc;
     using PP::ra; using PP::rb; using PP::avo; using PP::bvo;
-    f32x16 accx;
-    int xoff, xx, xvo;
+    // Accumulators: 16 x 16 blocks (f32x4).  c[in][im][sn][sm] is the block of columns wn + 32 in + 16 sn .. + 15 and rows
+    // wm + 32 im + 16 sm .. + 15; lane (l15, kg) holds row 16 sm + l15, columns 16 sn + 4 kg + e (TR: column 16 sn + l15, rows
+    // 16 sm + 4 kg + e).  cx[sn][sm]: the strip's block, rows 256 + 16 sm .., columns wn + 32 wr + 16 sn ...  PP::acc is not used.
+    f32x4 c[2][4][2][2], cx[2][2];
+    int l15, kg, a16, b16, x16, cxr, xvo;
 
     __device__ __forceinline__ void init(char* smem_) {
         PP::init(smem_);
-        xoff = 4 * HALF + l31 * 128;                            // strip row l31 inside a parity
-        xx = hi ^ PP::swz(l31);
+        l15 = lane & 15;
+        kg = lane >> 4;
+        // fragment reads: 16 rows x 32 k, lane (l15, kg) reads chunk (4 j + kg) ^ swz(row) of row base + l15.  Every base is a
+        // multiple of 16 rows, so swz(row) = swz(l15) and the chunk is (4 j) ^ cxr
+        a16 = (wr * 64 + l15) * 128;                            // row inside an A half-tile (+ 16 rows per block)
+        b16 = 2 * HALF + ((wave & 3) * 32 + l15) * 128;         // row inside a B half-tile
+        x16 = 4 * HALF + l15 * 128;                             // strip row inside a parity
+        cxr = kg ^ PP::swz(l15);
     }
     __device__ __forceinline__ void set_tile(const GemmDesc& P, const T* A, const T* B, int m0, int n0) {
         PP::set_tile(P, A, B, m0, n0);
@@ -1066,9 +1094,22 @@ struct PingPongX : PingPong<T> {
         xvo = min(256 + lrow, P.m - 1 - m0) * (P.lda * 2) + c * 16;
     }
     __device__ __forceinline__ void zero_acc() {
-        PP::zero_acc();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) accx[r] = 0.f;
+        for (int i = 0; i < 32; ++i) (&c[0][0][0][0])[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) (&cx[0][0])[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // mfma_fence for the 36 blocks
+    __device__ __forceinline__ void fence() {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) asm volatile("" : "+v"((&c[0][0][0][0])[i]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"((&cx[0][0])[i]));
+        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < 32; ++i) asm volatile("" : "+v"((&c[0][0][0][0])[i]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"((&cx[0][0])[i]));
     }
     // the four half-tiles live at the same offsets as in PingPong, parities are STGX apart
     __device__ __forceinline__ void xdma_half(const int Q, int t, int kb) {     // Q is a literal at every call site
@@ -1085,9 +1126,26 @@ struct PingPongX : PingPong<T> {
         char* dst = smem + (t & 1) * STGX + 4 * HALF + wave * 1024;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, xvo, (kb + t) * 128, 0, 0);
     }
-    __device__ __forceinline__ void read_x(T8 (&fx)[4], const char* st) {
+    // fa[eb][j]: A block eb (16 rows) of half h, k 32 j .. + 31;  fb[2 jh + sn][j]: B block sn of half jh;  fx[sm][j]: the strip
+    __device__ __forceinline__ void read_a16(T8 (&fa)[4][2], const char* st, int h) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) fx[ks] = *reinterpret_cast<const T8*>(st + xoff + (((2 * ks) ^ xx) << 4));
+        for (int eb = 0; eb < 4; ++eb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                fa[eb][j] = *reinterpret_cast<const T8*>(st + h * HALF + a16 + eb * 2048 + (((4 * j) ^ cxr) << 4));
+    }
+    __device__ __forceinline__ void read_b16(T8 (&fb)[4][2], const char* st) {
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                fb[bb][j] = *reinterpret_cast<const T8*>(st + b16 + (bb >> 1) * HALF + (bb & 1) * 2048 + (((4 * j) ^ cxr) << 4));
+    }
+    __device__ __forceinline__ void read_x16(T8 (&fx)[2][2], const char* st) {
+#pragma unroll
+        for (int sm = 0; sm < 2; ++sm)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fx[sm][j] = *reinterpret_cast<const T8*>(st + x16 + sm * 2048 + (((4 * j) ^ cxr) << 4));
     }
     // counted wait of a read slot: waves 0 - 3 carry one more DMA (the strip piece) per K tile in the A group
     template <int N>
@@ -1116,12 +1174,12 @@ struct PingPongX : PingPong<T> {
         }
         PP::slot();
         if (WR == 1) PP::slot();            // the second group runs one barrier behind
-        T8 fa[2][4], fb[2][4], fx[4];
+        T8 fa[4][2], fb[4][2], fx[2][2];
         auto body = [&](int kt, auto more1_t, auto more2_t) __attribute__((always_inline)) {
             constexpr bool M1 = decltype(more1_t)::value, M2 = decltype(more2_t)::value;   // tile kt + 1 / kt + 2 exists
             const char* st = smem + (kt & 1) * STGX;
-            this->read_b(fb, st);
-            this->read_a(fa, st, 0);
+            read_b16(fb, st);
+            read_a16(fa, st, 0);
             if (M1) {
                 xdma_half(2, kt + 1, kb); xdma_half(3, kt + 1, kb); if (xw) dma_strip(kt + 1, kb);
                 wait_rd<8>(xw);
@@ -1130,13 +1188,14 @@ struct PingPongX : PingPong<T> {
             }
             PP::slot();
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int ks = i >> 2, in = (i >> 1) & 1, e = i & 1;
-                acc[in][e] = TR ? mfma32(fa[e][ks], fb[in][ks], acc[in][e]) : mfma32(fb[in][ks], fa[e][ks], acc[in][e]);
+            for (int i = 0; i < 32; ++i) {                                          // a block comes round every 16th issue
+                const int j = i >> 4, bb = (i >> 2) & 3, eb = i & 3;
+                f32x4& d = c[bb >> 1][eb >> 1][bb & 1][eb & 1];
+                d = TR ? mfma16(fa[eb][j], fb[bb][j], d) : mfma16(fb[bb][j], fa[eb][j], d);
             }
             PP::slot();
-            this->read_a(fa, st, 1);
-            read_x(fx, st);
+            read_a16(fa, st, 1);
+            read_x16(fx, st);
             if (M2) {
                 xdma_half(0, kt + 2, kb); xdma_half(1, kt + 2, kb);
                 wait_rd<6>(xw);
@@ -1147,11 +1206,14 @@ struct PingPongX : PingPong<T> {
             }
             PP::slot();
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int ks = i >> 2, in = (i >> 1) & 1, e = i & 1;
-                acc[in][2 + e] = TR ? mfma32(fa[e][ks], fb[in][ks], acc[in][2 + e]) : mfma32(fb[in][ks], fa[e][ks], acc[in][2 + e]);
-                if ((i & 3) == 3)                                               // the strip's block: this wave's own B fragment
-                    accx = TR ? mfma32(fx[ks], fb[WR][ks], accx) : mfma32(fb[WR][ks], fx[ks], accx);
+            for (int i = 0; i < 32; ++i) {
+                const int j = i >> 4, bb = (i >> 2) & 3, eb = i & 3;
+                f32x4& d = c[bb >> 1][2 + (eb >> 1)][bb & 1][eb & 1];
+                d = TR ? mfma16(fa[eb][j], fb[bb][j], d) : mfma16(fb[bb][j], fa[eb][j], d);
+                if ((i & 3) == 3) {                                             // the strip's blocks: this wave's own B half WR
+                    const int s = i >> 2, js = s >> 2, sn = (s >> 1) & 1, sm = s & 1;      // a block comes round every 20th issue
+                    cx[sn][sm] = TR ? mfma16(fx[sm][js], fb[2 * WR + sn][js], cx[sn][sm]) : mfma16(fb[2 * WR + sn][js], fx[sm][js], cx[sn][sm]);
+                }
             }
             PP::slot();
         };
@@ -1189,10 +1251,7 @@ struct PingPongX : PingPong<T> {
         constexpr int NTHR = 512, BN = 256, CLDT = BMX + 8;
         static_assert((size_t)BN * CLDT * 2 + LNS <= SMEMX, "transposed C tile fits");
         T* Cs = reinterpret_cast<T*>(smem);        // [BN][CLDT]: n-major
-        mfma_fence(acc);
-        asm volatile("" : "+v"(accx));
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        asm volatile("" : "+v"(accx));
+        fence();
         const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
         const int side = stats ? P.ln_side : 0;    // 1 only (the activation is A): statistics per m, weight constants per n
         float* const lnr = reinterpret_cast<float*>(smem + (size_t)BN * CLDT * 2);    // [BMX][2] row statistics
@@ -1206,39 +1265,50 @@ struct PingPongX : PingPong<T> {
             }
             __syncthreads();
         }
-        // one 32 x 32 block: column cb + l31, tile rows rb + 8 gq + 4 hi + e
-        auto stage = [&](const f32x16& a, int rb, int cb) __attribute__((always_inline)) {
-            const int col = cb + l31;
-            const float bv = (bias && n0 + col < P.n) ? (float)bias[n0 + col] : 0.f;
-            float cs = 0.f, sh = 0.f;
-            if (side) { cs = lnc[2 * col]; sh = lnc[2 * col + 1]; }
+        // one 16 x 16 block: column `col` (= block column + l15), tile rows ml .. ml + 3 (= block row + 4 kg + e)
+        auto stage = [&](const f32x4& a, int ml, int col, float bv, float cs, float sh) __attribute__((always_inline)) {
+            f32x4 v = a;
+            if (side) {
+                const f32x4 p0 = *reinterpret_cast<const f32x4*>(lnr + 2 * ml);          // (mean, rstd) of rows ml, ml + 1
+                const f32x4 p1 = *reinterpret_cast<const f32x4*>(lnr + 2 * ml + 4);
+                const float mu[4] = {p0[0], p0[2], p1[0], p1[2]}, rs[4] = {p0[1], p0[3], p1[1], p1[3]};
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int ml = rb + gq * 8 + hi * 4;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = a[gq * 4 + e];
-                if (side) {
-                    const f32x4 p0 = *reinterpret_cast<const f32x4*>(lnr + 2 * ml);          // (mean, rstd) of rows ml, ml + 1
-                    const f32x4 p1 = *reinterpret_cast<const f32x4*>(lnr + 2 * ml + 4);
-                    const float mu[4] = {p0[0], p0[2], p1[0], p1[2]}, rs[4] = {p0[1], p0[3], p1[1], p1[3]};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float t = fmaf(-mu[e], cs, v[e]);
-                        asm volatile("" : "+v"(t));
-                        v[e] = fmaf(rs[e], t, sh);
-                    }
+                for (int e = 0; e < 4; ++e) {
+                    float t = fmaf(-mu[e], cs, v[e]);
+                    asm volatile("" : "+v"(t));
+                    v[e] = fmaf(rs[e], t, sh);
                 }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], P.scale, bv);
-                *reinterpret_cast<T4*>(Cs + col * CLDT + ml) = cvt4<T>(v);
             }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], P.scale, bv);
+            *reinterpret_cast<T4*>(Cs + col * CLDT + ml) = cvt4<T>(v);
+        };
+        // the column's constants (bias, colsum, shift) once per 16-column block
+        auto column = [&](int col, float& bv, float& cs, float& sh) __attribute__((always_inline)) {
+            bv = (bias && n0 + col < P.n) ? (float)bias[n0 + col] : 0.f;
+            cs = 0.f; sh = 0.f;
+            if (side) { cs = lnc[2 * col]; sh = lnc[2 * col + 1]; }
         };
 #pragma unroll
         for (int in = 0; in < 2; ++in)
 #pragma unroll
-            for (int im = 0; im < 4; ++im) stage(acc[in][im], wm + im * 32, wn + in * 32);
-        stage(accx, 256, wn + wr * 32);
+            for (int sn = 0; sn < 2; ++sn) {
+                const int col = wn + in * 32 + sn * 16 + l15;
+                float bv, cs, sh;
+                column(col, bv, cs, sh);
+#pragma unroll
+                for (int im = 0; im < 4; ++im)
+#pragma unroll
+                    for (int sm = 0; sm < 2; ++sm) stage(c[in][im][sn][sm], wm + im * 32 + sm * 16 + kg * 4, col, bv, cs, sh);
+            }
+#pragma unroll
+        for (int sn = 0; sn < 2; ++sn) {
+            const int col = wn + wr * 32 + sn * 16 + l15;
+            float bv, cs, sh;
+            column(col, bv, cs, sh);
+#pragma unroll
+            for (int sm = 0; sm < 2; ++sm) stage(cx[sn][sm], 256 + sm * 16 + kg * 4, col, bv, cs, sh);
+        }
         __syncthreads();
         // Fast path: frames at least as long as the tile (the tile touches at most two frames: one compare instead of a division
         // per chunk), all 18 LDS reads up front, then the stores.  Thread -> (staged row `col` = id / 36, chunk of 8 keys).
@@ -1279,17 +1349,59 @@ struct PingPongX : PingPong<T> {
     __device__ __forceinline__ void stage_x_fast(const GemmDesc& P, T* Cs, int n0, const float* lnr, const float* lnc) {
         const T* bias = reinterpret_cast<const T*>(P.bias);
         const float scale = P.scale;
-        f32x4 bvx[4];
+        // one 16 x 16 block (stage_block_fast for the 16x16x32 layout): row `row` (= block row + l15), columns nl .. nl + 3
+        // (= block column + 4 kg + e); bv, c0, c1: bias and LayerNorm constants of those four columns
+        auto stage = [&](const f32x4& a, int row, int nl, const f32x4& bv, const float (&c0)[4], const float (&c1)[4]) __attribute__((always_inline)) {
+            f32x4 v = a;
+            if (SIDE) {
+                const float lr0 = lnr[2 * row], lr1 = lnr[2 * row + 1];
 #pragma unroll
-        for (int in = 0; in < 2; ++in) {
-            f32x4 bv[4];
-            bias_block<T>(bv, bias, n0 + wn + in * 32 + hi * 4);
+                for (int e = 0; e < 4; ++e) {               // scalar FMAs on purpose, see Engine::store_tile
+                    float t = SIDE == 1 ? fmaf(-lr0, c0[e], v[e]) : fmaf(-c0[e], lr0, v[e]);
+                    asm volatile("" : "+v"(t));
+                    v[e] = SIDE == 1 ? fmaf(lr1, t, c1[e]) : fmaf(c1[e], t, lr1);
+                }
+            }
 #pragma unroll
-            for (int im = 0; im < 4; ++im)
-                stage_block_fast<T, SIDE>(Cs, CLD, acc[in][im], wm + im * 32 + l31, wn + in * 32 + hi * 4, scale, bv, lnr, lnc);
+            for (int e = 0; e < 4; ++e) {
+                float t = fmaf(v[e], scale, bv[e]);
+                asm volatile("" : "+v"(t));                 // see stage_block_fast
+                v[e] = t;
+            }
+            *reinterpret_cast<T4*>(Cs + row * CLD + nl) = cvt4<T>(v);
+        };
+        // the constants of the four columns nl .. nl + 3, once per 16-column block
+        auto columns = [&](int nl, f32x4& bv, float (&c0)[4], float (&c1)[4]) __attribute__((always_inline)) {
+            bv = bias ? up4<T>(*reinterpret_cast<const T4*>(bias + n0 + nl)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (SIDE) {
+                const f32x4 p0 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl);          // (c0, c1) of columns nl, nl + 1
+                const f32x4 p1 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl + 4);      // nl + 2, nl + 3
+                c0[0] = p0[0]; c0[1] = p0[2]; c0[2] = p1[0]; c0[3] = p1[2];
+                c1[0] = p0[1]; c1[1] = p0[3]; c1[2] = p1[1]; c1[3] = p1[3];
+            }
+        };
+#pragma unroll
+        for (int in = 0; in < 2; ++in)
+#pragma unroll
+            for (int sn = 0; sn < 2; ++sn) {
+                const int nl = wn + in * 32 + sn * 16 + kg * 4;
+                f32x4 bv;
+                float c0[4] = {0.f, 0.f, 0.f, 0.f}, c1[4] = {0.f, 0.f, 0.f, 0.f};
+                columns(nl, bv, c0, c1);
+#pragma unroll
+                for (int im = 0; im < 4; ++im)
+#pragma unroll
+                    for (int sm = 0; sm < 2; ++sm) stage(c[in][im][sn][sm], wm + im * 32 + sm * 16 + l15, nl, bv, c0, c1);
+            }
+#pragma unroll
+        for (int sn = 0; sn < 2; ++sn) {                                         // the strip's blocks: columns of B half wr
+            const int nl = wn + wr * 32 + sn * 16 + kg * 4;
+            f32x4 bv;
+            float c0[4] = {0.f, 0.f, 0.f, 0.f}, c1[4] = {0.f, 0.f, 0.f, 0.f};
+            columns(nl, bv, c0, c1);
+#pragma unroll
+            for (int sm = 0; sm < 2; ++sm) stage(cx[sn][sm], 256 + sm * 16 + l15, nl, bv, c0, c1);
         }
-        bias_block<T>(bvx, bias, n0 + wn + wr * 32 + hi * 4);                    // the strip's block: columns of B fragment wr
-        stage_block_fast<T, SIDE>(Cs, CLD, accx, 256 + l31, wn + wr * 32 + hi * 4, scale, bvx, lnr, lnc);
     }
 
     // Epilogue of Engine::store_tile for nine blocks per wave and 288 tile rows.
@@ -1297,10 +1409,7 @@ struct PingPongX : PingPong<T> {
                                                const float* stats = nullptr) {
         constexpr int NTHR = 512, BN = 256;
         T* Cs = reinterpret_cast<T*>(smem);        // [BMX][CLD]
-        mfma_fence(acc);
-        asm volatile("" : "+v"(accx));
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        asm volatile("" : "+v"(accx));
+        fence();
         const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
         const bool bias_vec = (reinterpret_cast<uintptr_t>(bias) & 7) == 0;
         const int side = stats ? P.ln_side : 0;
@@ -1336,48 +1445,50 @@ struct PingPongX : PingPong<T> {
             }
             __syncthreads();
         }
-        // one 32 x 32 accumulator block: tile rows rb + l31, columns cb + 8 gq + 4 hi + e
-        auto stage = [&](const f32x16& a, int rb, int cb) __attribute__((always_inline)) {
-            const int row = rb + l31;
+        // one 16 x 16 accumulator block: tile row rb + l15, columns cb + 4 kg + e
+        auto stage = [&](const f32x4& a, int rb, int cb) __attribute__((always_inline)) {
+            const int row = rb + l15;
             float lr0 = 0.f, lr1 = 0.f;
             if (side) { lr0 = lnr[2 * row]; lr1 = lnr[2 * row + 1]; }
+            const int nl = cb + kg * 4;
+            f32x4 v = a;
+            if (side) {
+                const f32x4 p0 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl);
+                const f32x4 p1 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl + 4);
+                const float lc0[4] = {p0[0], p0[2], p1[0], p1[2]}, lc1[4] = {p0[1], p0[3], p1[1], p1[3]};
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int nl = cb + gq * 8 + hi * 4;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = a[gq * 4 + e];
-                if (side) {
-                    const f32x4 p0 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl);
-                    const f32x4 p1 = *reinterpret_cast<const f32x4*>(lnc + 2 * nl + 4);
-                    const float lc0[4] = {p0[0], p0[2], p1[0], p1[2]}, lc1[4] = {p0[1], p0[3], p1[1], p1[3]};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {       // scalar FMAs on purpose (Engine::store_tile)
-                        float t = side == 1 ? fmaf(-lr0, lc0[e], v[e]) : fmaf(-lc0[e], lr0, v[e]);
-                        asm volatile("" : "+v"(t));
-                        v[e] = side == 1 ? fmaf(lr1, t, lc1[e]) : fmaf(lc1[e], t, lr1);
-                    }
+                for (int e = 0; e < 4; ++e) {       // scalar FMAs on purpose (Engine::store_tile)
+                    float t = side == 1 ? fmaf(-lr0, lc0[e], v[e]) : fmaf(-lc0[e], lr0, v[e]);
+                    asm volatile("" : "+v"(t));
+                    v[e] = side == 1 ? fmaf(lr1, t, lc1[e]) : fmaf(lc1[e], t, lr1);
                 }
-                f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-                if (bias) {
-                    if (bias_vec && n0 + nl + 4 <= P.n) {
-                        bv = up4<T>(*reinterpret_cast<const T4*>(bias + n0 + nl));
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n0 + nl + e < P.n) bv[e] = (float)bias[n0 + nl + e];
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], P.scale, bv[e]);
-                *reinterpret_cast<T4*>(Cs + row * CLD + nl) = cvt4<T>(v);
             }
+            f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+            if (bias) {
+                if (bias_vec && n0 + nl + 4 <= P.n) {
+                    bv = up4<T>(*reinterpret_cast<const T4*>(bias + n0 + nl));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (n0 + nl + e < P.n) bv[e] = (float)bias[n0 + nl + e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], P.scale, bv[e]);
+            *reinterpret_cast<T4*>(Cs + row * CLD + nl) = cvt4<T>(v);
         };
 #pragma unroll
         for (int in = 0; in < 2; ++in)
 #pragma unroll
-            for (int im = 0; im < 4; ++im) stage(acc[in][im], wm + im * 32, wn + in * 32);
-        stage(accx, 256, wn + wr * 32);
+            for (int im = 0; im < 4; ++im)
+#pragma unroll
+                for (int sn = 0; sn < 2; ++sn)
+#pragma unroll
+                    for (int sm = 0; sm < 2; ++sm) stage(c[in][im][sn][sm], wm + im * 32 + sm * 16, wn + in * 32 + sn * 16);
+#pragma unroll
+        for (int sn = 0; sn < 2; ++sn)
+#pragma unroll
+            for (int sm = 0; sm < 2; ++sm) stage(cx[sn][sm], 256 + sm * 16, wn + wr * 32 + sn * 16);
         __syncthreads();
         const bool vec_ok = (P.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
         constexpr int CPRW = BN / 8;               // 16-B chunks per C row
