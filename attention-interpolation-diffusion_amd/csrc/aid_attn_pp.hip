@@ -1,15 +1,21 @@
 // Ping-pong attention core for head dim 64 and whole 64-key tiles — plain attention (de-activated passes, reference
 // interpolation.py:581-584), the PLAIN riders of a batched-CFG call, and the interpolated frames of INNER / OUTER calls
 // (interpolation.py:626-664, 760-790) as ONE tile stream over the frame's key segments.  Same arithmetic as aid_attn_kernel (swapped
-// products, -m folded into the score MFMAs' accumulator, lazy row reference; the row sums here are sums of the ROUNDED P — bf16: eight
-// 4x4x4 MFMAs against a ones operand behind the PV MFMAs, f16: v_dot2c in the V slot — not a ones-row block); what differs is WHO does
-// what WHEN:
+// products, -m folded into the score MFMAs' accumulator, lazy row reference; the row sums here are sums of the ROUNDED P — bf16: four
+// MFMAs of a ones operand against P^T behind the PV MFMAs, f16: v_dot2c in the V slot — not a ones-row block); what differs is WHO does
+// what WHEN, and the product shape: both products are v_mfma_f32_16x16x32 (aid_attn_kernel: 32x32x16).  The M slot is bound by the
+// power-limited clock, not by issue, and the chip holds a higher clock under the 16x16x32 stream (tools/ubench/mfma_shape.hip, feed
+// `attn`; profiles/mfma_shape.txt, profiles/attn_pp_mfma16_ab.txt).  A wave's 32 query rows are two 16-row blocks; a lane serves one
+// row of each and shares it with three other lanes (lane ^ 16, ^ 32, ^ 48), which hold the other keys resp. channels of the row:
+// the row state (m, row sum, parked copies, -m blocks) is per row block, and raise() / finish() / swap_sides() cross the four lane
+// groups for the row maximum resp. the f16 row sum — on the rare paths only; the fast path's tests are wave-wide as before.
 //
 //   One workgroup = 8 waves x 32 query rows of one (frame, head); waves w and w + 4 share a SIMD.  Waves 0-3 and waves 4-7
 //   run the same program ONE BARRIER APART, and the program alternates two slots per 64-key tile:
-//     M(t)   every MFMA of the tile in one burst: S(t) = K(t) Q'^T - m (8), then O^T += V^T(t-1) P(t-1)^T (8); in their shadow,
-//            one per MFMA and in pinned program order, the 16 operand-fragment reads: V^T(t-1) beside the score MFMAs, K(t+1)
-//            beside the PV MFMAs into the registers the score MFMAs released (bf16: + the eight row-sum MFMAs).  No VALU instruction.
+//     M(t)   every MFMA of the tile in one burst: S(t) = K(t) Q'^T - m (4 key blocks x 2 row blocks x 2 k-steps = 32), then
+//            O^T += V^T(t-1) P(t-1)^T (4 channel blocks x 2 row blocks x 2 k-steps = 32); in their shadow, one beside every second
+//            MFMA and in pinned program order, the 16 operand-fragment reads: V^T(t-1) beside the score MFMAs, K(t+1) beside
+//            the PV MFMAs into the registers the score MFMAs released (bf16: + the four row-sum MFMAs).  No VALU instruction.
 //     V(t)   the VALU half: P(t) = 2^S(t), rounding to the storage type, the head-room test (bf16: on the exponent bits of the packed P,
 //            f16: on the tile's row sum, formed here with v_dot2c); plus this wave's two LDS-DMA pieces of tile t + 6 and the counted
 //            wait that retires its pieces of tile t + 3
@@ -119,7 +125,6 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     // no exponent range to spare for the bias (and its PV product would meet subnormal P): it keeps the row-sum test.
     constexpr bool SUMM = std::is_same<T, bf16>::value;
     constexpr float XB = SUMM ? XTH - 1.f : 0.f;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
 #ifdef AID_ABLATIONS
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
-    const int l31 = lane & 31, hi = lane >> 5;
+    const int l15 = lane & 15, lg = lane >> 4;                  // mfma16: column (query row of a 16-row block) and lane group
 
     // ---- work items: 256 query rows of one (frame, head).
     // p.persist == 0: one item per workgroup in hardware dispatch order; logical order [head][frame][q block], every XCD a contiguous
@@ -269,6 +274,7 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     adopt();
 
     // ---- Q fragments (B operand of the swapped product) -----------------------------------------
+    // qf[2 rb + ks]: row block rb (rows 16 rb + l15 of the wave's 32), k-step ks (channels 32 ks + 8 lg .. + 7)
     T8 qf[4];
     auto scale_q = [&]() __attribute__((always_inline)) {       // generic callers: fold softmax_scale * log2(e) into Q here (one extra
         if (!a.q_prescaled) {                                   // rounding; the processor path does it in the q projection's epilogue)
@@ -282,10 +288,13 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         }
     };
     {                                                           // the first item's rows: straight from global memory
-        const int qr = min(q0 + l31, a.s - 1);                  // rows past the end are clamped, never stored
-        const T* qrow = reinterpret_cast<const T*>(a.q) + (int64_t)fr * a.q_fs + (int64_t)qr * a.ldq + h * D;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const T8*>(qrow + ks * 16 + hi * 8);
+        for (int rb = 0; rb < 2; ++rb) {
+            const int qr = min(q0 + 16 * rb + l15, a.s - 1);    // rows past the end are clamped, never stored
+            const T* qrow = reinterpret_cast<const T*>(a.q) + (int64_t)fr * a.q_fs + (int64_t)qr * a.ldq + h * D;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) qf[2 * rb + ks] = *reinterpret_cast<const T8*>(qrow + ks * 32 + lg * 8);
+        }
         scale_q();
     }
 
@@ -295,17 +304,20 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     const Rsrc rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.vt), 0, 0x7fffffff, 0x00020000);
     const Rsrc rk2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.k2), 0, 0x7fffffff, 0x00020000);
     const Rsrc rv2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.vt2), 0, 0x7fffffff, 0x00020000);
-    // the NEXT item's Q rows wait in LDS behind the ring (8 waves x 4 KB, already in fragment order: piece ks of a wave = its 64 lanes'
-    // 16 B of k-step ks), fetched by DMA while the current item runs — no registers held for them
+    // the NEXT item's Q rows wait in LDS behind the ring (8 waves x 4 KB, already in fragment order: piece 2 rb + ks of a wave = its 64
+    // lanes' 16 B of row block rb, k-step ks), fetched by DMA while the current item runs — no registers held for them
     const Rsrc rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.q), 0, 0x7fffffff, 0x00020000);
     char* const qlds = smem + 2 * PNS * PTILE + wave * 4096;
     auto dma_q_next = [&]() __attribute__((always_inline)) {
-        const int qr = min(N_q0 + l31, a.s - 1);
-        const int vo = qr * (a.ldq * 2) + hi * 16;
         const int so = (int)(((int64_t)N_fr * a.q_fs + N_h * D) * 2);
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (__attribute__((address_space(3))) void*)(qlds + ks * 1024), 16, vo, so + ks * 32, 0, 0);
+        for (int rb = 0; rb < 2; ++rb) {
+            const int qr = min(N_q0 + 16 * rb + l15, a.s - 1);
+            const int vo = qr * (a.ldq * 2) + lg * 16;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (__attribute__((address_space(3))) void*)(qlds + (2 * rb + ks) * 1024), 16, vo, so + ks * 64, 0, 0);
+        }
     };
     const int prow = 8 * wave + (lane >> 3);                    // tile row this lane fetches
     const int pch = (lane & 7) ^ ((prow >> 1) & 7);             // logical 16-B chunk stored at slot lane & 7 (XOR swizzle)
@@ -344,44 +356,64 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     };
     bool has_next = false;
 
-    // ---- fragment read offsets: K rows with key bits 2 <-> 3 swapped (so P comes out in B-operand order), V^T rows = channels
-    const int krow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
-    const int kx = hi ^ ((krow >> 1) & 7), vx = hi ^ ((l31 >> 1) & 7);      // swz(r + 32) == swz(r)
-    const int koff = krow * 128, voff = PNS * PTILE + l31 * 128;
-    // LDS: the K tiles of the eight stages in [0, 64 KB), the V^T tiles in [64 KB, 128 KB): per-lane address of k-step ks in the
-    // register (< 4 KB, resp. 64 KB + < 4 KB), stage * 8 KB + block * 4 KB in the 16-bit offset field (<= 61440)
-    int kad[4], vad[4];
+    // ---- fragment read offsets (a fragment = 16 rows x 32 k, 16 B per lane: chunk 4 ks + lg of the lane's row) ------------------
+    // K: the lane's A row i = l15 of key block kb is the KEY 32 (kb >> 1) + 8 (i >> 2) + 4 ((i >> 1) & 1) + 2 (kb & 1) + (i & 1).  A lane
+    // receives D rows 4 lg + r of a score block — with this map, of blocks kb = 2 ks and 2 ks + 1, the keys 32 ks + 8 lg + {0, 1, 4, 5}
+    // and + {2, 3, 6, 7}: together eight consecutive keys, exactly the eight k values 8 lg .. 8 lg + 7 of k-step ks the lane supplies as
+    // B operand of the PV product.  P goes from the score registers to the PV operand with no cross-lane movement (the 32x32x16 form of
+    // this was "key bits 2 <-> 3 swapped").  Why pairs of keys alternate between the two blocks: the sixteen lanes a ds_read_b128
+    // serves together ({0-3, 12-15, 20-27} and so on) then hit sixteen different (row parity, slot) positions under the ring's XOR
+    // swizzle; with keys 4 b .. 4 b + 3 in block b every read was a two-way bank conflict (tests/test_attn_pp_mfma16_layout.py).
+    // V^T: row = channel 16 cb + l15, plain.
+    // LDS: the K tiles of the eight stages in [0, 64 KB), the V^T tiles in [64 KB, 128 KB): per-lane address of (k-step, kb & 1) resp.
+    // of the k-step in the register (< 4 KB, resp. 64 KB + < 2 KB), stage * 8 KB + (kb >> 1) * 4 KB resp. + cb * 2 KB in the 16-bit
+    // offset field (<= 63488)
+    int kad[4], vad[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        kad[ks] = koff + (((2 * ks) ^ kx) << 4);
-        vad[ks] = voff + (((2 * ks) ^ vx) << 4);
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int krow = 8 * (l15 >> 2) + 4 * ((l15 >> 1) & 1) + 2 * b + (l15 & 1);      // swz(r + 32) == swz(r)
+            kad[2 * ks + b] = krow * 128 + (((4 * ks + lg) ^ ((krow >> 1) & 7)) << 4);
+        }
+        vad[ks] = PNS * PTILE + l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) << 4);    // swz(r + 16) == swz(r)
     }
 
     // ---- online-softmax state -----------------------------------------------------------------------
-    float m = 0.f;
+    // A lane serves TWO query rows, 16 rb + l15 of row block rb = 0, 1, and shares each with the lanes l15 + 16 {0 .. 3} (a row's 64
+    // keys of a tile are spread over the four lane groups): everything per row is per row block, and equal in the four lanes.
+    //   sc[2 kb + rb][r]  score of key 32 (kb >> 1) + 8 lg + 4 (r >> 1) + 2 (kb & 1) + (r & 1)          o[2 cb + rb][r]  channel 16 cb + 4 lg + r
+    float m[2] = {0.f, 0.f};
     bool fresh = true;
-    f32x16 o[2], sc[2];
-    float lsum = 0.f;                   // row sum of the ROUNDED P over the 32 keys per tile this lane holds (the partner lane has the others)
-    f32x4 lacc = {0.f, 0.f, 0.f, 0.f};  // SUMM: the same sum as the D block of the 4x4x4 MFMAs (four equal copies; lsum unused)
-    s16x4 ones4;                        // SUMM: A operand of those MFMAs, 4 x 4 ones per block
+    f32x4 o[8], sc[8];
+    float lsum[2] = {0.f, 0.f};         // f16: row sum of the ROUNDED P over the 16 keys per tile this lane holds (the other three groups have the rest)
+    f32x4 lrs[2];                       // SUMM: the row sum as the D block of ones x P^T MFMAs — the WHOLE row's sum, in all four registers of all
+                                        // four lanes of the row (lsum unused)
+    T8 ones8;                           // SUMM: A operand of those MFMAs
 #pragma unroll
-    for (int i = 0; i < 4; ++i) ones4[i] = 0x3f80;
-    asm volatile("" : "+v"(ones4));
-    auto get_l = [&]() __attribute__((always_inline)) -> float { return SUMM ? lacc[0] : lsum; };
-    auto set_l = [&](float x) __attribute__((always_inline)) {
-        if (SUMM) { lacc[0] = x; lacc[1] = x; lacc[2] = x; lacc[3] = x; } else lsum = x;
+    for (int i = 0; i < 8; ++i) ones8[i] = (T)1.0f;
+    asm volatile("" : "+v"(ones8));
+    // the lane's register of the row sum (what park keeps), and the row's whole sum
+    auto get_l = [&](int rb) __attribute__((always_inline)) -> float { return SUMM ? lrs[rb][0] : lsum[rb]; };
+    auto row_l = [&](int rb) __attribute__((always_inline)) -> float { return SUMM ? lrs[rb][0] : sum_groups4(lsum[rb]); };
+    auto set_l = [&](int rb, float x) __attribute__((always_inline)) {
+        if (SUMM) { lrs[rb][0] = x; lrs[rb][1] = x; lrs[rb][2] = x; lrs[rb][3] = x; } else lsum[rb] = x;
     };
-    T8 pf[4];
-    f32x16 cneg;                        // -m as an accumulator block (C operand of a tile's first score MFMAs), rebuilt when m moves
-    f32x16 po[2];                       // parked: O of the own-keys state while the begin side runs, then the finished begin side
-    float pl = 0.f, pm = 0.f;           // parked row sum (this lane's register of the row-sum block) and row reference
+    T8 pf[4];                           // pf[2 rb + ks][e]: P of key 32 ks + 8 lg + e
+    f32x4 cneg[2];                      // -m as accumulator blocks (C operand of a tile's first score MFMAs), rebuilt when m moves
+    f32x4 po[8];                        // parked: O of the own-keys state while the begin side runs, then the finished begin side
+    float pl[2] = {0.f, 0.f}, pm[2] = {0.f, 0.f};   // parked row sum (this lane's register of it) and row reference
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; cneg[r] = 0.f; }
-    if (MODE == AID_MODE_OUTER) {
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { po[0][r] = 0.f; po[1][r] = 0.f; }
+        for (int r = 0; r < 4; ++r) { o[i][r] = 0.f; if (MODE == AID_MODE_OUTER) po[i][r] = 0.f; }
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        set_l(rb, 0.f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cneg[rb][r] = 0.f;
     }
-    asm volatile("" : "+v"(cneg));
+    asm volatile("" : "+v"(cneg[0]), "+v"(cneg[1]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) pf[i] = zero8<T>();
 
@@ -428,78 +460,89 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
 #endif
 
     // MFMA results and the VALU code that reads them.  The hazard recogniser does not see across the slots' barriers / branches
-    // (aid_attn.hip has the history), so the distance is kept by hand: an 8-pass MFMA's result may be read 11 wait states (of four
-    // cycles) after its issue.  `sc` is read by the next V slot — behind the eight PV MFMAs that follow the score MFMAs in every M slot
-    // and a barrier (>= 48 cycles): no padding needed in the loop, only the compiler is told not to move anything across (tie).
+    // (aid_attn.hip has the history), so the distance is kept by hand: a 4-pass MFMA's result may be read 7 wait states (of four
+    // cycles) after its issue (an 8-pass one's, as the 32x32x16 kernel issued, 11).  `sc` is read by the next V slot — behind the sixteen
+    // PV MFMAs that follow the score MFMAs in every M slot and a barrier: no padding needed in the loop, only the compiler is told not
+    // to move anything across (tie).
     // `o` / the row-sum block are read by the rare paths only (raise, park, swap_sides, finish): THEY start with the padding (settle)
     // — 20 wait states per M slot were 76 cycles of every 1120-cycle interval (tools/ubench/barrier_cost.hip).  The prologue's S(0)
     // has nothing behind it and is settled as before.
     auto tie = [&]() __attribute__((always_inline)) {
-        asm volatile("" : "+v"(sc[0]), "+v"(sc[1]));
-        asm volatile("" : "+v"(o[0]), "+v"(o[1]));
-        if (SUMM) asm volatile("" : "+v"(lacc));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(sc[i]), "+v"(o[i]));
+        if (SUMM) asm volatile("" : "+v"(lrs[0]), "+v"(lrs[1]));
     };
     auto settle = [&]() __attribute__((always_inline)) {
         tie();
         asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
         tie();
     };
-    // operand fragments: kf = K(t + 1) for S(t + 1), vf = V^T(t) for O += V^T(t) P(t)^T, all four k-steps each
-    T8 kf[4][2], vf[4][2];
-    auto lds_k = [&](int st, int ks, int b) __attribute__((always_inline)) {           // st: ring stage, a constant wherever it matters
-        return *reinterpret_cast<const T8*>(smem + kad[ks] + (st * PTILE + b * 4096));
+    // operand fragments: kf = K(t + 1) for S(t + 1), vf = V^T(t) for O += V^T(t) P(t)^T; [k-step][key block resp. channel block]
+    T8 kf[2][4], vf[2][4];
+    auto lds_k = [&](int st, int ks, int kb) __attribute__((always_inline)) {          // st: ring stage, a constant wherever it matters
+        return *reinterpret_cast<const T8*>(smem + kad[2 * ks + (kb & 1)] + (st * PTILE + (kb >> 1) * 4096));
     };
-    auto lds_v = [&](int st, int kk, int d) __attribute__((always_inline)) {
-        return *reinterpret_cast<const T8*>(smem + vad[kk] + (st * PTILE + d * 4096));
+    auto lds_v = [&](int st, int ks, int cb) __attribute__((always_inline)) {
+        return *reinterpret_cast<const T8*>(smem + vad[ks] + (st * PTILE + cb * 2048));
     };
     auto pin = []() __attribute__((always_inline)) { __builtin_amdgcn_sched_barrier(0); };
 
-    // M slot of the main loop — S(t + 1) = K(t + 1) Q'^T - m, then O^T += V^T(t) P(t)^T — and the fragment reads that ride in its
-    // shadow, one per MFMA, program order pinned:  V^T(t) (stage sv) beside the eight score MFMAs, which use the K fragments read
-    // one M slot ago; K(t + 2) (stage sk) beside PV MFMAs 2 .. 9, into the registers the score MFMAs have released.  No VALU.
+    // M slot of the main loop — S(t + 1) = K(t + 1) Q'^T - m (4 key blocks x 2 row blocks x 2 k-steps = 32 MFMAs), then
+    // O^T += V^T(t) P(t)^T (4 channel blocks x 2 row blocks x 2 k-steps = 32; bf16: + 4 row-sum MFMAs, ones x P^T) — and the sixteen
+    // fragment reads that ride in its shadow, one beside every second MFMA, program order pinned:  V^T(t) (stage sv) beside the score
+    // MFMAs, which use the K fragments read one M slot ago; K(t + 2) (stage sk) beside the PV MFMAs, into the registers the score MFMAs
+    // have released.  Every block's first k-step is issued before any second one: the two MFMAs that chain through one accumulator
+    // are eight issues apart (the row-sum blocks likewise).  No VALU.
     auto mslot = [&](int sv, int sk) __attribute__((always_inline)) {
 #ifdef AID_ABLATIONS
         if (p.abl & 4) {                                        // 4: no MFMA slot at all
-            asm volatile("" : "+v"(sc[0]), "+v"(sc[1]));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(sc[i]));
             return;
         }
 #endif
         pin();
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int ks = i >> 1, b = i & 1;
+        for (int i = 0; i < 16; ++i) {                          // i = 8 ks + 2 kb + rb
+            const int ks = i >> 3, kb = (i >> 1) & 3, rb = i & 1;
+            if (!(i & 1)) {
+                const int n = i >> 1;                           // V^T fragments in the order the PV MFMAs use them
 #ifdef AID_ABLATIONS
-            if (!((p.abl & 64) && b))                           // 64: half the fragment reads (is the M slot bound by the LDS port?)
+                if (!((p.abl & 64) && (n & 1)))                 // 64: half the fragment reads (is the M slot bound by the LDS port?)
 #endif
-            vf[ks][b] = lds_v(sv, ks, b);
-            pin();
-            sc[b] = mfma32(kf[ks][b], qf[ks], ks ? sc[b] : cneg);
+                vf[n >> 2][n & 3] = lds_v(sv, n >> 2, n & 3);
+                pin();
+            }
+            sc[2 * kb + rb] = mfma16(kf[ks][kb], qf[2 * rb + ks], ks ? sc[2 * kb + rb] : cneg[rb]);
             pin();
         }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kk = i >> 1, w = i & 1;
-            o[w] = mfma32(vf[kk][w], pf[kk], o[w]);
+        for (int i = 0; i < 16; ++i) {                          // i = 8 ks + 2 cb + rb
+            const int ks = i >> 3, cb = (i >> 1) & 3, rb = i & 1;
+            o[2 * cb + rb] = mfma16(vf[ks][cb], pf[2 * rb + ks], o[2 * cb + rb]);
             pin();
-            if constexpr (SUMM) {                               // l += the lane's four P values of half w of k-step kk (D[i][j] = sum_k B[k][j])
-                const u32x4 w4 = __builtin_bit_cast(u32x4, pf[kk]);
-                u32x2 h2;
-                h2[0] = w4[2 * w]; h2[1] = w4[2 * w + 1];
-                lacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones4, __builtin_bit_cast(s16x4, h2), lacc, 0, 0, 0);
+            if constexpr (SUMM) {                               // l += the row's 32 P values of k-step ks' (D[i][j] = sum_k B[k][j], any i)
+                if ((i & 3) == 3) {
+                    const int j = i >> 2, rs = j & 1, kq = j >> 1;
+                    lrs[rs] = mfma16(ones8, pf[2 * rs + kq], lrs[rs]);
+                    pin();
+                }
+            }
+            if (i & 1) {
+                const int n = i >> 1;                           // (kf[n >> 2][n & 3] was released by score MFMA 2 n + 1, sixteen or more MFMAs ago)
+#ifdef AID_ABLATIONS
+                if (!((p.abl & 64) && (n & 1)))
+#endif
+                kf[n >> 2][n & 3] = lds_k(sk, n >> 2, n & 3);
                 pin();
             }
-#ifdef AID_ABLATIONS
-            if (!((p.abl & 64) && w))
-#endif
-            kf[kk][w] = lds_k(sk, kk, w);                       // (kf[kk][w] was released by score MFMA 2 kk + w, eight or more MFMAs ago)
-            pin();
         }
     };
 
     // V slot: P(t) = 2^S(t) (row reference raised first when the head-room of the storage type is exceeded), rounded to the storage
     // type; this wave's two DMA pieces of tile t + LEAD; the counted wait that retires its pieces of tile t + 3.
-    // bf16: 32 v_exp + 16 v_cvt_pk + 8 v_or3 / v_bitop3 + 1 compare — the row sums are the M slot's (eight 4x4x4 MFMAs of 8 cycles behind
-    // the PV MFMAs; 16 v_dot2c + 2 v_mov + 2 v_add less here: -0.4 ... -4 % per launch, profiles/r04_attn_notes.txt table 5).
+    // bf16: 32 v_exp + 16 v_cvt_pk + 8 v_or3 / v_bitop3 + 1 compare — the row sums are the M slot's (four ones x P^T MFMAs of 16 cycles
+    // behind the PV MFMAs; 16 v_dot2c + 2 v_mov + 2 v_add less here: -0.4 ... -4 % per launch, profiles/r04_attn_notes.txt table 5).
     // (The requests stay HERE: issued from the M slot they cost 3 - 18 %, table 4.)
     constexpr int LEAD = 6;
     // (The counted wait behind an item boundary stays vmcnt(6) although the finished item's stores and the next Q request then sit in
@@ -519,73 +562,75 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         if (!(p.abl & 2))
 #endif
         dma_next((t + LEAD) & (PNS - 1));
-        // P(t) = 2^S(t) rounded to the storage type (lane (q, hi): sc[b][r] belongs to key 32 b + 16 (r >> 3) + 8 hi + (r & 7) of the tile
-        // = k-step 2 b + (r >> 3) of PV), and the tile's row sum of the ROUNDED values: v_dot2c against (1, 1), two keys per instruction,
-        // on two accumulators (the matrix pipe's ones-row block cost 4 of 20 MFMAs)
-        auto exp_tile = [&]() __attribute__((always_inline)) -> float {
-            float t0 = 0.f, t1 = 0.f;
+        // P(t) = 2^S(t) rounded to the storage type (pf[2 rb + ks][e] = 2^sc[2 (2 ks + ((e >> 1) & 1)) + rb][(e & 1) + 2 (e >> 2)]: key 32 ks + 8 lg + e), and the
+        // tile's row sums of the ROUNDED values, one per row block: v_dot2c against (1, 1), two keys per instruction (the matrix pipe's
+        // ones-row block cost 4 of 20 MFMAs)
+        auto exp_frag = [&](int rb, int ks) __attribute__((always_inline)) -> u32x4 {
+            f32x8 pv;
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+            for (int e = 0; e < 8; ++e) pv[e] = __builtin_amdgcn_exp2f(sc[2 * (2 * ks + ((e >> 1) & 1)) + rb][(e & 1) + 2 * (e >> 2)]);
+            pf[2 * rb + ks] = cvt8<T>(pv);
+            return __builtin_bit_cast(u32x4, pf[2 * rb + ks]);
+        };
+        auto exp_tile = [&](float& s0, float& s1) __attribute__((always_inline)) {
+            float t[2] = {0.f, 0.f};
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    f32x8 pv;
+            for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pv[e] = __builtin_amdgcn_exp2f(sc[b][8 * u + e]);
-                    pf[2 * b + u] = cvt8<T>(pv);
-                    const u32x4 w4 = __builtin_bit_cast(u32x4, pf[2 * b + u]);
-                    t0 = dot2_ones<T>(w4[0], t0); t1 = dot2_ones<T>(w4[1], t1);
-                    t0 = dot2_ones<T>(w4[2], t0); t1 = dot2_ones<T>(w4[3], t1);
+                for (int rb = 0; rb < 2; ++rb) {
+                    const u32x4 w4 = exp_frag(rb, ks);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) t[rb] = dot2_ones<T>(w4[e], t[rb]);
                 }
-            return t0 + t1;
+            s0 = t[0]; s1 = t[1];
         };
         // SUMM: the same without the sums — they are formed from pf in the M slot — returning the OR of the 16 packed words instead
         // (v_or3_b32): a value >= 2 anywhere shows in bit 14 of one of its halves (P >= 0: no other value has that bit)
         auto exp_tile_or = [&]() __attribute__((always_inline)) -> uint32_t {
             uint32_t acc = 0;
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+            for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    f32x8 pv;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) pv[e] = __builtin_amdgcn_exp2f(sc[b][8 * u + e]);
-                    pf[2 * b + u] = cvt8<T>(pv);
-                    const u32x4 w4 = __builtin_bit_cast(u32x4, pf[2 * b + u]);
-                    acc = (b == 0 && u == 0) ? (w4[0] | w4[1] | w4[2]) | w4[3] : (acc | w4[0] | w4[1]) | (w4[2] | w4[3]);
+                for (int rb = 0; rb < 2; ++rb) {
+                    const u32x4 w4 = exp_frag(rb, ks);
+                    acc = (ks == 0 && rb == 0) ? (w4[0] | w4[1] | w4[2]) | w4[3] : (acc | w4[0] | w4[1]) | (w4[2] | w4[3]);
                 }
             return acc;
         };
-        auto row_max = [&]() __attribute__((always_inline)) -> float {
-            float xm = fmaxf(sc[0][0], sc[0][1]);
+        // the lane's maximum of the tile's scores of row block rb (16 keys; the row's other 48 are in the other three lane groups)
+        auto row_max = [&](int rb) __attribute__((always_inline)) -> float {
+            float xm = fmaxf(sc[rb][0], sc[rb][1]);
 #ifdef AID_ABLATIONS
             if (!(p.abl & 8))                                   // 8: no head-room check (the maximum chain)
 #endif
 #pragma unroll
-            for (int i = 1; i < 16; ++i) xm = fmaxf(fmaxf(xm, sc[i >> 3][(2 * i) & 15]), sc[i >> 3][(2 * i + 1) & 15]);
+            for (int i = 1; i < 8; ++i) xm = fmaxf(fmaxf(xm, sc[2 * (i >> 1) + rb][(2 * i) & 3]), sc[2 * (i >> 1) + rb][(2 * i + 1) & 3]);
             return xm;
         };
         // slow path (first tile of the row, or a score out-grew the head-room of the storage type): move the reference to the row
-        // maximum, rescale O and l and shift this tile's arguments; PV(t - 1) is complete, O is at rest
-        auto raise = [&](float xm) __attribute__((always_inline)) {
+        // maximum — per row block, over the four lane groups that share the row — rescale O and l and shift this tile's arguments;
+        // PV(t - 1) is complete, O is at rest
+        auto raise = [&]() __attribute__((always_inline)) {
             settle();
-            const float rowmax = max_halves(xm) + XB;           // (SUMM: the row maximum lands at -XB)
-            const float shift = fresh ? rowmax : fmaxf(rowmax, 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-shift);
-            m += shift;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) cneg[r] = -m;
-            asm volatile("" : "+v"(cneg));                      // (opaque: keeps hipcc from rebuilding the block in every M slot)
+            for (int rb = 0; rb < 2; ++rb) {
+                const float rowmax = max_groups4(row_max(rb)) + XB;     // (SUMM: the row maximum lands at -XB)
+                const float shift = fresh ? rowmax : fmaxf(rowmax, 0.f);
+                const float alpha = __builtin_amdgcn_exp2f(-shift);
+                m[rb] += shift;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-            if (SUMM) lacc *= alpha; else lsum *= alpha;
+                for (int r = 0; r < 4; ++r) cneg[rb][r] = -m[rb];
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+                for (int cb = 0; cb < 4; ++cb) o[2 * cb + rb] *= alpha;
+                if (SUMM) lrs[rb] *= alpha; else lsum[rb] *= alpha;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sc[b][r] -= shift;
+                for (int kb = 0; kb < 4; ++kb) sc[2 * kb + rb] -= shift;
+            }
+            asm volatile("" : "+v"(cneg[0]), "+v"(cneg[1]));    // (opaque: keeps hipcc from rebuilding the blocks in every M slot)
             fresh = false;
         };
         // Exponentiate first, test afterwards: the scores stay intact in `sc`, so a tile whose row sum shows that an argument out-grew
-        // the head-room (sum of this lane's 32 values above 2^XTH; an f32 / storage-type overflow arrives as +inf and tests true as well)
+        // the head-room (sum of this lane's 16 values of a row above 2^XTH; an f32 / storage-type overflow arrives as +inf and tests true as well)
         // is simply redone against the raised reference.  The sixteen v_max3 of a per-tile maximum chain become one compare:
         // -2.7 ... -3.1 % per launch (profiles/r04_attn_notes.txt); every P that reaches the PV product is <= 2^XTH as before.
         // (`fresh` is set where an item or a pure OUTER side starts: tile 0 of a trip.  `first` is a constant in each unrolled copy,
@@ -594,16 +639,18 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         if constexpr (SUMM) {
             const uint32_t orw = fr ? 0u : exp_tile_or();
             if (__builtin_expect(fr || __any((orw & 0x40004000u) != 0u), 0)) {
-                raise(row_max());
+                raise();
                 exp_tile_or();
             }
         } else {
-            float ts = fr ? 0.f : exp_tile();
-            if (__builtin_expect(fr || __any(ts > __builtin_amdgcn_exp2f(XTH)), 0)) {
-                raise(row_max());
-                ts = exp_tile();
+            float ts0 = 0.f, ts1 = 0.f;
+            if (!fr) exp_tile(ts0, ts1);
+            if (__builtin_expect(fr || __any(fmaxf(ts0, ts1) > __builtin_amdgcn_exp2f(XTH)), 0)) {
+                raise();
+                exp_tile(ts0, ts1);
             }
-            lsum += ts;
+            lsum[0] += ts0;
+            lsum[1] += ts1;
         }
         wait_vm<6>();                                           // retires tile t + 3: the three tiles behind it stay in flight
     };
@@ -613,37 +660,34 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     auto park = [&]() __attribute__((always_inline)) {          // own keys done: park the state, the begin side continues on it
         settle();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { po[0][r] = o[0][r]; po[1][r] = o[1][r]; }
-        pl = get_l();
-        pm = m;
+        for (int i = 0; i < 8; ++i) po[i] = o[i];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) { pl[rb] = get_l(rb); pm[rb] = m[rb]; }
     };
     auto swap_sides = [&]() __attribute__((always_inline)) {    // begin side done: keep (1 - c) O_b / l_b, resume the own-keys state
         settle();
-        const float lown = get_l();
-        const float lrow = lown + other_half(lown);             // (all lanes take part in the exchange)
-        const float wb = w_b / lrow;
 #pragma unroll
-        for (int d = 0; d < 2; ++d)
+        for (int rb = 0; rb < 2; ++rb) {
+            const float wb = w_b / row_l(rb);                   // (all lanes take part in the exchange)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float rb = o[d][r] * wb;
-                o[d][r] = po[d][r];
-                po[d][r] = rb;
+            for (int cb = 0; cb < 4; ++cb) {
+                const f32x4 rbk = o[2 * cb + rb] * wb;
+                o[2 * cb + rb] = po[2 * cb + rb];
+                po[2 * cb + rb] = rbk;
             }
-        set_l(pl);
-        const float back = m - pm;                              // S(t) was formed against the begin side's reference (>= the parked one)
-        m = pm;
+            set_l(rb, pl[rb]);
+            const float back = m[rb] - pm[rb];                  // S(t) was formed against the begin side's reference (>= the parked one)
+            m[rb] = pm[rb];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cneg[r] = -m;
-        asm volatile("" : "+v"(cneg));
+            for (int r = 0; r < 4; ++r) cneg[rb][r] = -m[rb];
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sc[b][r] += back;
+            for (int kb = 0; kb < 4; ++kb) sc[2 * kb + rb] += back;
+        }
+        asm volatile("" : "+v"(cneg[0]), "+v"(cneg[1]));
         if (park_at < 0) fresh = true;                          // pure OUTER: the end side starts from the empty state
     };
 
-    // O / l of the finished item; lane (q = l31, hi) holds dv = 32 d + 8 g + 4 hi + {0..3}.  The wave's 32 x 64 block goes through ITS
+    // O / l of the finished item; lane (l15, lg) holds channels 16 cb + 4 lg + {0..3} of rows 16 rb + l15.  The wave's 32 x 64 block goes through ITS
     // 4 KB of LDS behind the ring (the next item's Q rows were read out of it before the last M slot; a persistent walk requests the
     // item after that only at the top of the next item) and leaves as four 16-byte stores per lane covering whole 128-byte rows: eight
     // 8-byte stores per lane at a row stride are store-ISSUE bound (~1.4 us per item measured on the short-stream kernel; the guide's T21).
@@ -661,40 +705,38 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
             return;
         }
 #endif
-        const float lown = get_l();
-        const float inv = w_e / (lown + other_half(lown));      // (w_e = 1 unless this frame mixes two sides)
+        float inv[2];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) inv[rb] = w_e / row_l(rb);       // (w_e = 1 unless this frame mixes two sides; all lanes take part)
         if (q0 >= a.s) return;                                  // (wave-uniform: a wave past the last row)
         const float osc = a.out_scale * (a.frame_scale ? PP_LDU(a.frame_scale, fr) : 1.f);
         if (MODE == AID_MODE_OUTER) {
             // (the OUTER instantiation sits at 250 of 256 registers with the parked state: it keeps the 8-byte row-per-lane stores — its
             //  items are two or three key segments long, the store tail is <= 3 % of an item)
-            const int q = q0 + l31;
-            if (q < a.s) {
-                T* orow = reinterpret_cast<T*>(a.out) + (int64_t)fr * a.o_fs + (int64_t)q * a.ldo + h * D;
 #pragma unroll
-                for (int d = 0; d < 2; ++d)
+            for (int rb = 0; rb < 2; ++rb) {
+                const int q = q0 + 16 * rb + l15;
+                if (q < a.s) {
+                    T* orow = reinterpret_cast<T*>(a.out) + (int64_t)fr * a.o_fs + (int64_t)q * a.ldo + h * D;
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int dv_ = 32 * d + 8 * g + 4 * hi;
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = (o[d][4 * g + e] * inv + po[d][4 * g + e]) * osc;      // po: the begin side, or zero
+                    for (int cb = 0; cb < 4; ++cb) {
+                        const int dv_ = 16 * cb + 4 * lg;
+                        f32x4 v = (o[2 * cb + rb] * inv[rb] + po[2 * cb + rb]) * osc;       // po: the begin side, or zero
                         if (a.accumulate) v += up4<T>(*reinterpret_cast<const T4*>(orow + dv_));
                         *reinterpret_cast<T4*>(orow + dv_) = cvt4<T>(v);
                     }
+                }
             }
         } else {
-            // stage: 16-byte chunk c = 4 d + g of row r sits at slot c ^ swz(r) (two-way conflicts at most on the 8-byte writes)
+            // stage: 16-byte chunk c = 2 cb + (lg >> 1) of row r = 16 rb + l15 sits at slot c ^ swz(r), the lane's 8 bytes in half lg & 1
             char* const st = qlds;
-            const int wsw = (l31 >> 1) & 7;
+            const int wsw = (l15 >> 1) & 7;                     // swz(r + 16) == swz(r)
 #pragma unroll
-            for (int d = 0; d < 2; ++d)
+            for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = o[d][4 * g + e] * inv * osc;
-                    *reinterpret_cast<T4*>(st + l31 * 128 + (((4 * d + g) ^ wsw) << 4) + 8 * hi) = cvt4<T>(v);
+                for (int cb = 0; cb < 4; ++cb) {
+                    const f32x4 v = o[2 * cb + rb] * inv[rb] * osc;
+                    *reinterpret_cast<T4*>(st + (16 * rb + l15) * 128 + (((2 * cb + (lg >> 1)) ^ wsw) << 4) + 8 * (lg & 1)) = cvt4<T>(v);
                 }
             // read back row-major: lane -> (row lane / 8 + 8 i, chunk lane % 8), one whole 128-byte row per eight lanes
             const Rsrc ro = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7fffffff, 0x00020000);     // (built here: no SGPRs held across the item)
@@ -731,19 +773,20 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
     slot_barrier();
     if (grp == 1) slot_barrier();                               // the second group runs one barrier behind
 #pragma unroll
-    for (int i = 0; i < 8; ++i) kf[i >> 1][i & 1] = lds_k(0, i >> 1, i & 1);
-    f32x16 zacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zacc[r] = 0.f;
+    for (int i = 0; i < 8; ++i) kf[i >> 2][i & 3] = lds_k(0, i >> 2, i & 3);
+    const f32x4 zacc = {0.f, 0.f, 0.f, 0.f};
 #ifdef AID_ABLATIONS
     if (!(p.abl & 4))
 #endif
     {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) sc[i & 1] = mfma32(kf[i >> 1][i & 1], qf[i >> 1], (i >> 1) ? sc[i & 1] : zacc);      // m = 0
+        for (int i = 0; i < 16; ++i) {                          // i = 8 ks + 2 kb + rb, as in the M slot; m = 0
+            const int ks = i >> 3, kb = (i >> 1) & 3, rb = i & 1;
+            sc[2 * kb + rb] = mfma16(kf[ks][kb], qf[2 * rb + ks], ks ? sc[2 * kb + rb] : zacc);
+        }
         pin();
 #pragma unroll
-        for (int i = 0; i < 8; ++i) kf[i >> 1][i & 1] = lds_k(1, i >> 1, i & 1);      // nt >= 2
+        for (int i = 0; i < 8; ++i) kf[i >> 2][i & 3] = lds_k(1, i >> 2, i & 3);      // nt >= 2
     }
     settle();
     slot_barrier();
@@ -792,10 +835,10 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
 #pragma unroll                                                  // its Q rows, and a zero row reference like a fresh workgroup's
                         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const T8*>(qlds + ks * 1024 + lane * 16);
                         scale_q();
-                        m = 0.f;                                // (the finished item needs O and the row sums only)
+                        m[0] = 0.f; m[1] = 0.f;                 // (the finished item needs O and the row sums only)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) cneg[r] = 0.f;
-                        asm volatile("" : "+v"(cneg));
+                        for (int r = 0; r < 4; ++r) { cneg[0][r] = 0.f; cneg[1][r] = 0.f; }
+                        asm volatile("" : "+v"(cneg[0]), "+v"(cneg[1]));
                     }
                     PP_STAMP(0);
                     if (i < 4) PP_BSTAMP(3 + 2 * i);
@@ -827,15 +870,12 @@ __global__ __launch_bounds__(512) void aid_attn_pp_kernel(const AttnPPParams p) 
         }
         // the next item: its S(0) is in `sc`; everything else starts over
         fresh = true;
-        set_l(0.f);
-        pl = 0.f;
-        pm = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
-        if (MODE == AID_MODE_OUTER) {
+        for (int rb = 0; rb < 2; ++rb) { set_l(rb, 0.f); pl[rb] = 0.f; pm[rb] = 0.f; }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { po[0][r] = 0.f; po[1][r] = 0.f; }
-        }
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { o[i][r] = 0.f; if (MODE == AID_MODE_OUTER) po[i][r] = 0.f; }
         adopt();
         dseg = 0;                                               // the DMA stream is LEAD tiles into this item's first segment already
     }

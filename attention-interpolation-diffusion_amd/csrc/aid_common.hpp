@@ -1,4 +1,4 @@
-// Shared device helpers for the gfx950 kernels (wave64, MFMA 32x32x16).
+// Shared device helpers for the gfx950 kernels (wave64, MFMA 32x32x16 and 16x16x32).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +34,15 @@ __device__ __forceinline__ f32x16 mfma32(const Vec<f16>::v8& a, const Vec<f16>::
 }
 __device__ __forceinline__ f32x16 mfma32(const Vec<bf16>::v8& a, const Vec<bf16>::v8& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+// D(16x16, fp32) += A(16x32) * B(32x16): half the flops of mfma32 in half the cycles.  Lane l supplies A[i = l&15][8*(l>>4) .. +7] and
+// B[8*(l>>4) .. +7][j = l&15]; lane l receives D[4*(l>>4) + r][l&15], r in [0,4).
+__device__ __forceinline__ f32x4 mfma16(const Vec<f16>::v8& a, const Vec<f16>::v8& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma16(const Vec<bf16>::v8& a, const Vec<bf16>::v8& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 template <typename T>
@@ -77,6 +86,17 @@ __device__ __forceinline__ float sum_halves(float x) {
     const uint32_t u = __float_as_uint(x);
     auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// Column j of an mfma16 D block lives in the four lanes j, j + 16, j + 32, j + 48: maximum / sum over them (every lane takes part and
+// gets the result; two ds_bpermute each — for the rare paths)
+__device__ __forceinline__ float max_groups4(float x) {
+    x = fmaxf(x, __shfl_xor(x, 16));
+    return fmaxf(x, __shfl_xor(x, 32));
+}
+__device__ __forceinline__ float sum_groups4(float x) {
+    x += __shfl_xor(x, 16);
+    return x + __shfl_xor(x, 32);
 }
 
 // Bijective XCD-aware remap of a 1-D grid: hardware places block b on XCD b % 8; give every

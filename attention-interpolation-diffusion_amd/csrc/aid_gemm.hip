@@ -1045,15 +1045,7 @@ static_assert(Engine<bf16, 128, 128, 64, PP_SMALL_NS, 2, 4>::SMEM <= PingPong<bf
 // (4 j + kg) ^ swz(row) of row base + l15, conflict-free under the ds_read_b128 lane groups), a phase is 32 MFMAs on sixteen
 // 16 x 16 blocks instead of 16 on four 32 x 32 blocks, the strip 8 per K tile on four blocks; fragment and accumulator registers
 // are unchanged (80 + 144).  Every block sums k in the same order as before, and the results are bit-identical to the 32x32x16
-// loop's on every shape measured (profiles/ppx_mfma16_ab.txt).
-// D(16x16, fp32) += A(16x32) * B(32x16).  Lane l supplies A[i = l&15][8*(l>>4) .. +7] and B[8*(l>>4) .. +7][j = l&15]; lane l
-// receives D[4*(l>>4) + r][l&15], r in [0,4).
-__device__ __forceinline__ f32x4 mfma16(const Vec<f16>::v8& a, const Vec<f16>::v8& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const Vec<bf16>::v8& a, const Vec<bf16>::v8& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+// loop's on every shape measured (profiles/ppx_mfma16_ab.txt).  (mfma16: aid_common.hpp.)
 
 template <typename T>
 struct PingPongX : PingPong<T> {

@@ -61,14 +61,7 @@ __device__ __forceinline__ void rs_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// D(16x16, fp32) += A(16x32) * B(32x16).  Lane l supplies A[i = l & 15][8 (l >> 4) .. + 7] and B[8 (l >> 4) .. + 7][j = l & 15];
-// lane l receives D[4 (l >> 4) + e][l & 15], e in [0, 4).
-__device__ __forceinline__ f32x4 mfma16(const Vec<f16>::v8& a, const Vec<f16>::v8& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const Vec<bf16>::v8& a, const Vec<bf16>::v8& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+// (the products are mfma16, aid_common.hpp: D(16x16, fp32) += A(16x32) * B(32x16))
 
 // LDS-DMA of one slice: a wave contributes PPW 1-KiB pieces.  `rs_src` resolves the slice (uniform: its problem's weight bytes), a
 // piece is one buffer_load ... lds.  (Unlike the global_load_lds builtin the buffer form does not make hipcc drain the whole DMA ring —
