@@ -11,8 +11,9 @@ interp.py (coefficients, slerp / lerp initialisation)  ·  attn_shim.py (diffuse
 dist.py (frame sharding over RCCL)  ·  loop.py (denoising-loop harness)  ·  sequence.py (batch assembly of
 interpolate_single / N-frame interpolate)  ·  endpoint_store.py (recorded end points: render further frames between them)  ·  keyframe_store.py (key frames recorded once: render between any two)  ·  pipelines.py (the reference's pipeline classes over components)  ·  prior.py (Beta-prior exploration of the coefficient path).
 """
-from .interp import generate_beta_tensor, linear_interpolation, slerp, spherical_interpolation
-from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
+from .interp import (generate_beta_tensor, grid_weights, linear_interpolation, nested_slerp, simplex_weights, slerp,
+                     spherical_interpolation)
+from .processors import (CornerInterpolatedAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
                          InnerInterpolatedIPAttnProcessor, InterpolatedAttnProcessor, OuterInterpolatedAttnProcessor,
                          OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, activate_aid,
                          clear_text_kv_cache, clear_weight_caches, deactivate_aid, load_aid, load_aid_ip_adapter)
@@ -26,7 +27,8 @@ from .pipelines import (DDIMSchedulerLite, InterpolationStableDiffusionPipeline,
                         InterpolationStableDiffusionXLPipeline, StackDenoiser)
 
 __all__ = [
-    "generate_beta_tensor", "linear_interpolation", "slerp", "spherical_interpolation",
+    "generate_beta_tensor", "linear_interpolation", "slerp", "spherical_interpolation", "grid_weights", "simplex_weights", "nested_slerp",
+    "CornerInterpolatedAttnProcessor",
     "InterpolatedAttnProcessor", "OuterInterpolatedAttnProcessor", "InnerInterpolatedAttnProcessor",
     "OuterInterpolatedIPAttnProcessor", "InnerInterpolatedIPAttnProcessor", "ScaleControlIPAttnProcessor",
     "HipAttnProcessor", "HipIPAdapterAttnProcessor", "load_aid", "load_aid_ip_adapter", "activate_aid", "deactivate_aid",

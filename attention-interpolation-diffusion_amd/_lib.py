@@ -26,6 +26,7 @@ EP_RECORD, EP_REPLAY = 1, 2
 KF_MAX_ROWS = 8
 KF_PUT, KF_GET = 0, 1
 KF_RECORD, KF_REPLAY = 1, 2
+MAX_CORNERS = 8
 
 # every symbol include/aid_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -33,6 +34,7 @@ ABI_SYMBOLS = (
     "aid_endpoint_rows", "aid_processor_ep_workspace_bytes", "aid_processor_ep_fwd",
     "aid_keyframe_rows", "aid_processor_kf_workspace_bytes", "aid_processor_kf_fwd",
     "aid_q8_block_bytes", "aid_keyframe_rows_q8", "aid_processor_kf_q8_workspace_bytes", "aid_processor_kf_q8_fwd",
+    "aid_mix_kv", "aid_corners_scratch_bytes", "aid_attn_corners_fwd", "aid_processor_corners_workspace_bytes", "aid_processor_corners_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -160,6 +162,13 @@ class AidKeyframeCall(C.Structure):
     ]
 
 
+class AidCorners(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(C.c_int32)), ("weights", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("n_corners", C.c_int32),
+    ]
+
+
 class AidProfileEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double),
                 ("flops_executed", C.c_double)]
@@ -253,6 +262,17 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_kf_q8_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall)]
     lib.aid_processor_kf_q8_fwd.restype = C.c_int
     lib.aid_processor_kf_q8_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeCall), C.c_void_p]
+    lib.aid_mix_kv.restype = C.c_int
+    lib.aid_mix_kv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+    lib.aid_corners_scratch_bytes.restype = C.c_size_t
+    lib.aid_corners_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.aid_attn_corners_fwd.restype = C.c_int
+    lib.aid_attn_corners_fwd.argtypes = [C.POINTER(AidAttnArgs), C.POINTER(AidCorners), C.c_void_p]
+    lib.aid_processor_corners_workspace_bytes.restype = C.c_size_t
+    lib.aid_processor_corners_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidCorners)]
+    lib.aid_processor_corners_fwd.restype = C.c_int
+    lib.aid_processor_corners_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidCorners), C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

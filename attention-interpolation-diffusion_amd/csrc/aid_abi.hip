@@ -137,13 +137,20 @@ int check_problem(const AidGemmProblem& q) {
 }
 
 struct Carve {
-    size_t q, k, vt, o, k2, vt2, xn, kip, vtip, ux, uctx, uo, total;
+    size_t q, k, vt, o, k2, vt2, xn, kip, vtip, ux, uctx, uo, ctab, total;
     int lp, tp;
     int rx, rctx;                                         // LoRA: columns of U of x / of ctx
 };
 
+// bytes of the pair table of a corner-weighted call (aid_hip.h): the INNER coefficient vector, then (coef_p, scale_p) per pass,
+// n_frames floats each
+size_t corner_table_bytes(int n_frames, int n_corners) {
+    return align_up((size_t)(1 + 2 * ((n_corners + 1) / 2)) * n_frames * sizeof(float), 256);
+}
+
 // kv_extra: rows of k / V^T behind the projected ones (end-point store replay: the begin and the end frame's)
-Carve carve(const AidProcessorArgs& a, int kv_extra = 0) {
+// corners: > 0 = a corner-weighted call among that many corners, whose pair table lies behind everything else
+Carve carve(const AidProcessorArgs& a, int kv_extra = 0, int corners = 0) {
     Carve c;
     const size_t es = a.dtype == AID_DTYPE_F32 ? 4 : 2;
     const int nctx = a.ctx ? a.n_ctx : a.n_frames;
@@ -174,6 +181,8 @@ Carve carve(const AidProcessorArgs& a, int kv_extra = 0) {
     if (c.rx) { c.ux = off; off += align_up((size_t)a.n_frames * a.s * c.rx * es, 256); }
     if (c.rctx) { c.uctx = off; off += align_up((size_t)a.n_ctx * a.l * c.rctx * es, 256); }
     if (a.lora_r_o) { c.uo = off; off += align_up((size_t)a.n_frames * a.s * a.lora_r_o * es, 256); }
+    c.ctab = off;
+    if (corners > 0) off += corner_table_bytes(a.n_frames, corners);
     c.total = off;
     return c;
 }
@@ -537,9 +546,8 @@ int aid_cfg_rescale(const void* text, const void* uncond, void* out, int32_t n, 
     return err == hipSuccess ? AID_OK : fail_hip(err, "aid_cfg_rescale");
 }
 
-int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
-    if (!args) return AID_ERR_ARG;
-    const AidAttnArgs& a = *args;
+// everything aid_attn_fwd refuses (aid_hip.h), before any launch
+static int check_attn(const AidAttnArgs& a) {
     if (!a.q || !a.k || !a.vt || !a.out) return AID_ERR_ARG;
     if (!dtype_ok(a.dtype)) return AID_ERR_DTYPE;
     if (a.mode < AID_MODE_PLAIN || a.mode > AID_MODE_OUTER) return AID_ERR_ARG;
@@ -560,6 +568,14 @@ int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
         if (a.bias_fs < 0 || a.bias_hs < 0 || a.bias_rs < 0) return AID_ERR_ARG;
         if (reinterpret_cast<uintptr_t>(a.bias) % (a.dtype == AID_DTYPE_F32 ? 4 : 2)) return AID_ERR_SHAPE;
     }
+    return AID_OK;
+}
+
+int aid_attn_fwd(const AidAttnArgs* args, void* stream) {
+    if (!args) return AID_ERR_ARG;
+    const AidAttnArgs& a = *args;
+    const int chk = check_attn(a);
+    if (chk != AID_OK) return chk;
     // algorithmic work: key segments per frame — plain 1, pure inner 1, fused inner 2,
     // pure outer 2, fused outer 3
     const int segs = a.mode == AID_MODE_PLAIN ? 1 : (a.mode == AID_MODE_INNER ? 1 : 2) + (a.fused ? 1 : 0);
@@ -645,9 +661,143 @@ int aid_lerp_kv(const void* k, const void* vt, void* k2, void* vt2, const float*
                         n_frames > 2 ? n_frames - 2 : 0);
 }
 
+// ---- corner-weighted AID (aid_hip.h) ---------------------------------------------------------------------------------------------
+static int check_mix(const void* k, const void* vt, const void* k2, const void* vt2, const int32_t* rows, const float* weights,
+                     int32_t n_frames, int32_t n_plain, int32_t n_corners, int64_t k_fs, int64_t vt_fs, int32_t dtype) {
+    if (!k || !vt || !k2 || !vt2 || !rows || !weights) return AID_ERR_ARG;
+    if (n_corners < 1 || n_corners > AID_MAX_CORNERS || n_frames < 1 || n_plain < 0 || n_plain > n_frames) return AID_ERR_ARG;
+    for (int m = 0; m < n_corners; ++m)
+        if (rows[m] < 0) return AID_ERR_ARG;
+    if (!dtype_ok(dtype)) return AID_ERR_DTYPE;
+    if (k_fs < 8 || vt_fs < 8 || k_fs % 8 || vt_fs % 8) return AID_ERR_SHAPE;
+    if (!aligned16(k) || !aligned16(vt) || !aligned16(k2) || !aligned16(vt2) || !aligned4(weights)) return AID_ERR_SHAPE;
+    return AID_OK;
+}
+
+static int mix_kv_impl(const void* k, const void* vt, void* k2, void* vt2, const int32_t* rows, const float* weights, int32_t n_frames,
+                       int32_t n_plain, int32_t n_corners, int64_t k_fs, int64_t vt_fs, int32_t dtype, void* stream) {
+    aid::CornerRows cr;
+    for (int m = 0; m < AID_MAX_CORNERS; ++m) cr.row[m] = rows[m < n_corners ? m : 0];
+    const int n_mix = n_frames - n_plain;
+    hipError_t e;
+    {
+        // traffic: the corner rows read once, one mixed row written per AID frame
+        const double elems = (double)(k_fs + vt_fs);
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_mix_kv<%s,m%d>", dtype_name(dtype), n_corners);
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 2.0 * n_corners * n_mix * elems,
+                     (dtype == AID_DTYPE_F32 ? 4.0 : 2.0) * ((double)n_corners + n_mix) * elems);
+        e = aid::mix_kv_launch(k, vt, k2, vt2, weights, cr, n_corners, n_mix, k_fs, vt_fs, dtype, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_mix_kv");
+}
+
+int aid_mix_kv(const void* k, const void* vt, void* k2, void* vt2, const int32_t* rows, const float* weights, int32_t n_frames,
+               int32_t n_plain, int32_t n_corners, int64_t k_fs, int64_t vt_fs, int32_t dtype, void* stream) {
+    const int rc = check_mix(k, vt, k2, vt2, rows, weights, n_frames, n_plain, n_corners, k_fs, vt_fs, dtype);
+    if (rc != AID_OK) return rc;
+    return mix_kv_impl(k, vt, k2, vt2, rows, weights, n_frames, n_plain, n_corners, k_fs, vt_fs, dtype, stream);
+}
+
+size_t aid_corners_scratch_bytes(int32_t n_frames, int32_t n_corners) {
+    if (n_frames < 1 || n_corners < 1 || n_corners > AID_MAX_CORNERS) return 0;
+    return corner_table_bytes(n_frames, n_corners);
+}
+
+// the AidCorners of a call over n_kv rows of k / V^T; `own_scratch`: the call brings the pair table's memory (aid_attn_corners_fwd)
+static int check_corners(const AidCorners& c, int n_frames, int n_kv, int n_plain, bool own_scratch) {
+    if (!c.rows || !c.weights || c.n_corners < 1 || c.n_corners > AID_MAX_CORNERS) return AID_ERR_ARG;
+    if (n_plain < 0 || n_plain > n_frames) return AID_ERR_ARG;
+    for (int m = 0; m < c.n_corners; ++m)
+        if (c.rows[m] < 0 || c.rows[m] >= n_kv) return AID_ERR_ARG;
+    if (!aligned4(c.weights)) return AID_ERR_SHAPE;
+    if (own_scratch) {
+        if (!c.scratch) return AID_ERR_ARG;
+        if (!aligned16(c.scratch)) return AID_ERR_SHAPE;
+        if (n_frames >= 1 && c.scratch_bytes < corner_table_bytes(n_frames, c.n_corners)) return AID_ERR_WORKSPACE;
+    }
+    return AID_OK;
+}
+
+// pass 0 of the composition as aid_attn_fwd sees it: what the checks of a corner call run on
+static AidAttnArgs corner_pass0(const AidAttnArgs& a, const AidCorners& c, const float* tab) {
+    AidAttnArgs at = a;
+    const bool outer = a.mode == AID_MODE_OUTER;
+    at.coef = outer ? tab + a.n_frames : tab;
+    at.frame_scale = outer ? tab + 2 * (size_t)a.n_frames : nullptr;
+    at.begin = c.rows[0];
+    at.end = outer && c.n_corners > 1 ? c.rows[1] : c.rows[0];
+    at.accumulate = 0;
+    at.out_scale = 1.f;
+    at.seg_executed = 0;
+    return at;
+}
+
+// the composition over aid_attn_fwd (aid_hip.h); `a` and `c` are checked, tab = the pair table's memory
+static int attn_corners_impl(const AidAttnArgs& a, const AidCorners& c, float* tab, void* stream) {
+    const int n = a.n_frames, n_mix = a.n_frames - a.n_plain, M = c.n_corners;
+    hipError_t e;
+    {
+        ProfScope ps(static_cast<hipStream_t>(stream), "aid_corner_pairs", 0.0, 4.0 * n * (M + 1.0 + 2.0 * ((M + 1) / 2)));
+        e = aid::corner_pairs_launch(c.weights, tab, n, n_mix, M, static_cast<hipStream_t>(stream));
+    }
+    if (e != hipSuccess) return fail_hip(e, "aid_attn_corners_fwd");
+    AidAttnArgs at = corner_pass0(a, c, tab);
+    if (a.mode == AID_MODE_INNER) {             // every AID frame reads its mixed row (coefficient 0.5), the riders their own keys
+        const int rc = mix_kv_impl(a.k, a.vt, const_cast<void*>(a.k2), const_cast<void*>(a.vt2), c.rows, c.weights, n, a.n_plain, M,
+                                   a.k_fs, a.vt_fs, a.dtype, stream);
+        if (rc != AID_OK) return rc;
+        return aid_attn_fwd(&at, stream);
+    }
+    int rc = aid_attn_fwd(&at, stream);         // OUTER pass 0: every frame, the riders with it
+    for (int p = 1; p < (M + 1) / 2 && rc == AID_OK && n_mix > 0; ++p) {        // pass p: the AID frames, accumulating
+        at.n_frames = n_mix;
+        at.n_plain = 0;
+        at.coef = tab + (size_t)(1 + 2 * p) * n;
+        at.frame_scale = tab + (size_t)(2 + 2 * p) * n;
+        at.begin = c.rows[2 * p];
+        at.end = 2 * p + 1 < M ? c.rows[2 * p + 1] : c.rows[2 * p];
+        at.accumulate = 1;
+        rc = aid_attn_fwd(&at, stream);
+    }
+    return rc;
+}
+
+int aid_attn_corners_fwd(const AidAttnArgs* args, const AidCorners* corners, void* stream) {
+    if (!args || !corners) return AID_ERR_ARG;
+    const AidAttnArgs& a = *args;
+    if (a.mode != AID_MODE_INNER && a.mode != AID_MODE_OUTER) return AID_ERR_ARG;
+    int rc = check_corners(*corners, a.n_frames, a.n_kv, a.n_plain, true);
+    if (rc != AID_OK) return rc;
+    float* tab = static_cast<float*>(corners->scratch);
+    const AidAttnArgs at = corner_pass0(a, *corners, tab);
+    rc = check_attn(at);
+    if (rc != AID_OK) return rc;
+    if (a.mode == AID_MODE_INNER) {
+        rc = check_mix(a.k, a.vt, a.k2, a.vt2, corners->rows, corners->weights, a.n_frames, a.n_plain, corners->n_corners, a.k_fs, a.vt_fs,
+                       a.dtype);
+        if (rc != AID_OK) return rc;
+    }
+    return attn_corners_impl(a, *corners, tab, stream);
+}
+
 size_t aid_processor_workspace_bytes(const AidProcessorArgs* args) {
     if (!args || check_processor(*args) != AID_OK) return 0;
     return carve(*args).total;
+}
+
+// The AidProcessorArgs a corner-weighted processor call is checked and carved with: coef / begin / end are not the caller's to give,
+// so the weights (a non-NULL device pointer; the pair table replaces it before any kernel reads a coefficient) and the first corner
+// stand in.  `extras`: image segments or a store came with the call.
+static int corners_processor_args(const AidProcessorArgs& a, const AidCorners& c, bool extras, AidProcessorArgs* out) {
+    if (a.mode != AID_MODE_INNER && a.mode != AID_MODE_OUTER) return AID_ERR_ARG;
+    if (a.ip || extras) return AID_ERR_ARG;
+    const int rc = check_corners(c, a.n_frames, a.ctx ? a.n_ctx : a.n_frames, a.n_plain, false);
+    if (rc != AID_OK) return rc;
+    *out = a;
+    out->coef = c.weights;
+    out->begin = out->end = c.rows[0];
+    return AID_OK;
 }
 
 int aid_endpoint_rows(const AidEndpointRows* args, void* stream) {
@@ -757,7 +907,7 @@ static int check_keyframe_call(const AidProcessorArgs& a, const AidKeyframeCall&
 }
 
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream, bool kf_q8 = false);
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8 = false, const AidCorners* cn = nullptr);
 
 size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidEndpointStore* ep) {
     if (!args) return 0;
@@ -800,11 +950,24 @@ int aid_processor_kf_q8_fwd(const AidProcessorArgs* args, const AidKeyframeCall*
     return processor_impl(args, nullptr, 0, nullptr, kf, stream, true);
 }
 
+size_t aid_processor_corners_workspace_bytes(const AidProcessorArgs* args, const AidCorners* corners) {
+    if (!args) return 0;
+    if (!corners) return aid_processor_workspace_bytes(args);
+    AidProcessorArgs a;
+    if (corners_processor_args(*args, *corners, false, &a) != AID_OK || check_processor(a) != AID_OK) return 0;
+    return carve(a, 0, corners->n_corners).total;
+}
+
+int aid_processor_corners_fwd(const AidProcessorArgs* args, const AidCorners* corners, void* stream) {
+    return processor_impl(args, nullptr, 0, nullptr, nullptr, stream, false, corners);
+}
+
 // ``ep`` / ``kf`` (at most one of them): which copy launch stands behind the projections — a pair store's aid_endpoint_rows, the
 // key-frame stores' aid_keyframe_rows or, with ``kf_q8``, aid_keyframe_rows_q8 on 8-bit block stores.  All replays are the same call:
 // two rows more of k / V^T, filled by that launch.
+// ``cn``: a corner-weighted call (aid_processor_corners_fwd) — step 2 is the composition among the corners, nothing else differs.
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream, bool kf_q8) {
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8, const AidCorners* cn) {
     if (!args) return AID_ERR_ARG;
     AidProcessorArgs a_local;
     const bool replay = (ep && ep->mode == AID_EP_REPLAY) || (kf && kf->mode == AID_KF_REPLAY);
@@ -812,7 +975,11 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         a_local = *args;                                  // store below); args->begin / args->end are not read
         a_local.begin = a_local.end = 0;
     }
-    const AidProcessorArgs& a = replay ? a_local : *args;
+    if (cn) {                                             // args->coef / begin / end are not read: the pair table stands in for them
+        const int rcc = corners_processor_args(*args, *cn, ip_segs != nullptr || n_ip_segs != 0 || ep || kf, &a_local);
+        if (rcc != AID_OK) return rcc;
+    }
+    const AidProcessorArgs& a = (replay || cn) ? a_local : *args;
     int rc = check_processor(a);
     if (rc != AID_OK) return rc;
     if (ep) {
@@ -830,7 +997,7 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         rc = check_ip_segments(ip_segs, n_ip_segs, a.n_frames);
         if (rc != AID_OK) return rc;
     }
-    const Carve cv = carve(a, replay ? 2 : 0);
+    const Carve cv = carve(a, replay ? 2 : 0, cn ? cn->n_corners : 0);
     if (!a.workspace || a.workspace_bytes < cv.total || !aligned16(a.workspace)) return AID_ERR_WORKSPACE;
     char* ws = static_cast<char*>(a.workspace);
     void* q = ws + cv.q;
@@ -1020,9 +1187,11 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         // begin / end are rows of k / vt (context rows when ctx_map is given); the interpolated rows are per FRAME
         at.k2 = ws + cv.k2; at.vt2 = ws + cv.vt2;
         const int interior = a.n_frames - a.n_plain - 2;
-        rc = lerp_kv_impl(k, vt, ws + cv.k2, ws + cv.vt2, a.coef, a.n_frames, begin, end, (int64_t)l * a.c,
-                          (int64_t)a.c * cv.lp, a.dtype, stream, interior > 0 ? interior : 0);
-        if (rc != AID_OK) return rc;
+        if (!cn) {                                            // (a corner call mixes its own rows, below)
+            rc = lerp_kv_impl(k, vt, ws + cv.k2, ws + cv.vt2, a.coef, a.n_frames, begin, end, (int64_t)l * a.c,
+                              (int64_t)a.c * cv.lp, a.dtype, stream, interior > 0 ? interior : 0);
+            if (rc != AID_OK) return rc;
+        }
     }
     at.coef = a.coef; at.frame_scale = nullptr; at.kv_map = a.ctx_map;
     at.n_frames = a.n_frames; at.n_kv = kv_rows;
@@ -1038,7 +1207,7 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
     at.q_prescaled = 1;
     at.seg_executed = a.seg_executed;
     at.f32_split = a.f32_attn_split;                          // (the image branch below copies it with the rest)
-    rc = aid_attn_fwd(&at, stream);
+    rc = cn ? attn_corners_impl(at, *cn, reinterpret_cast<float*>(ws + cv.ctab), stream) : aid_attn_fwd(&at, stream);
     if (rc != AID_OK) return rc;
 
     // 2b. IP-Adapter image branch: a second (short) attention launch that accumulates into o

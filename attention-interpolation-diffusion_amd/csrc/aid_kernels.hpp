@@ -208,6 +208,12 @@ hipError_t keyframe_rows_launch(const AidKeyframeRows& a, hipStream_t stream);
 // the same rows between a call and 8-bit block stores, quantised on PUT and dequantised on GET (aid_keyframe_q8.hip); arguments
 // checked by the caller
 hipError_t keyframe_rows_q8_launch(const AidKeyframeRowsQ8& a, hipStream_t stream);
+// corner-weighted AID (aid_corners.hip): the INNER mix among up to AID_MAX_CORNERS rows of k / vt into the first n_mix rows of
+// k2 / vt2, and the pair table of aid_attn_corners_fwd ([1 + 2 ceil(M / 2), n_frames] floats); arguments checked by the caller
+struct CornerRows { int32_t row[AID_MAX_CORNERS]; };          // by value in the kernel arguments
+hipError_t mix_kv_launch(const void* k, const void* vt, void* k2, void* vt2, const float* w, const CornerRows& rows, int n_corners,
+                         int n_mix, int64_t k_fs, int64_t vt_fs, int dtype, hipStream_t stream);
+hipError_t corner_pairs_launch(const float* w, float* tab, int n_frames, int n_mix, int n_corners, hipStream_t stream);
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,
                             int dtype, hipStream_t stream);
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);

@@ -22,7 +22,7 @@ from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
-from .processors import (HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
+from .processors import (CornerInterpolatedAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
                          InnerInterpolatedIPAttnProcessor, InterpolatedAttnProcessor, OuterInterpolatedAttnProcessor,
                          OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, cache_generation, clear_weight_caches)
 
@@ -94,6 +94,26 @@ def install_sequence_processors(unet, size: int, early: str = "fused_outer", alp
             p.size = size
             p.coef = coef.detach().to(torch.float32).cpu().clone()
         procs[name] = p
+    unet.set_attn_processor(procs)
+
+
+def install_corner_processors(unet, weights, corner_rows: Sequence[int], early: str = "fused_outer") -> None:
+    """One ``CornerInterpolatedAttnProcessor`` per attention layer: frame i of the batch interpolates among the corner frames
+    ``corner_rows`` with the weight row ``weights[i]`` (``[size, M]``, M <= 8), in the mode ``early`` names.  Every processor gets its own
+    copy of the weights (edit them per processor, or install again).  IP-Adapter layers are refused: the image branches interpolate
+    between two end points."""
+    if early not in EARLY_MODES:
+        raise ValueError(f"early must be one of {EARLY_MODES}")
+    current = dict(unet.attn_processors)
+    if any(_adapter_of(cur) is not None for cur in current.values()):
+        raise NotImplementedError("corner-weighted AID on a UNet with IP-Adapter layers: the image branches interpolate between two "
+                                  "end points only")
+    clear_weight_caches()
+    w = torch.as_tensor(weights, dtype=torch.float32).detach().cpu()
+    procs = {}
+    for name in current:
+        procs[name] = CornerInterpolatedAttnProcessor(w.clone(), corner_rows, mode=early.split("_")[1],
+                                                      is_fused=early.startswith("fused"), original_attn=HipAttnProcessor())
     unet.set_attn_processor(procs)
 
 

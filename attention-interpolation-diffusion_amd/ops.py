@@ -17,8 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME,
-                   KF_GET, KF_MAX_ROWS, KF_PUT, KF_RECORD, KF_REPLAY, MODE_INNER, MODE_OUTER, MODE_PLAIN,
-                   AidAttnArgs, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeCall,
+                   KF_GET, KF_MAX_ROWS, KF_PUT, KF_RECORD, KF_REPLAY, MAX_CORNERS, MODE_INNER, MODE_OUTER, MODE_PLAIN,
+                   AidAttnArgs, AidCorners, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeCall,
                    AidKeyframeRow, AidKeyframeRows, AidKeyframeRowsQ8, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
@@ -695,7 +695,7 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                   kv_cached: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   attn_bias: Optional[torch.Tensor] = None, lora=None, f32_precision: Optional[str] = None,
                   f32_attn_precision: Optional[str] = None, ip_segments: Optional[Sequence[dict]] = None,
-                  ep: Optional[dict] = None, kf: Optional[dict] = None) -> torch.Tensor:
+                  ep: Optional[dict] = None, kf: Optional[dict] = None, corners: Optional[dict] = None) -> torch.Tensor:
     """One whole processor call: y = to_out(AID-attention(to_q(x), to_k(ctx), to_v(ctx)))
     in three launches (grouped q/k/V^T GEMM, attention core, out-proj GEMM).
     ``ln = (gamma, beta, eps)`` computes on LayerNorm(x); ``residual`` is added to the result (the transformer
@@ -722,7 +722,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     one launch after the text attention — several IP-Adapters per layer, regional masks as ``row_weight``.  A cross-attention
     ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only.
     ``ep``: the end-point store of the layer, see ``processor_ep_fwd``.  ``kf``: key-frame stores of the layer, see
-    ``processor_kf_fwd`` (one of the two at most)."""
+    ``processor_kf_fwd`` (one of the two at most).  ``corners``: a corner-weighted call, see ``processor_corners_fwd`` (no store, no
+    image branch; ``coef`` / ``begin`` / ``end`` are not read)."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
     attn_split = f32_attn_split_code(f32_attn_precision)
@@ -836,10 +837,17 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     if dt == DTYPE_F32:
         a.f32_split = split
         a.f32_attn_split = attn_split
-    est = kcall = None
+    est = kcall = ccall = None
     if ep is not None and kf is not None:
         raise ValueError("a call takes an end-point store (ep=) or key-frame stores (kf=), not both")
-    if ep is not None:
+    if corners is not None:
+        if ep is not None or kf is not None or ip is not None or seg_arr is not None:
+            raise ValueError("a corner-weighted call takes no store and no image branch")
+        if mode == "plain":
+            raise ValueError("a corner-weighted call is an interpolated (inner / outer) call")
+        ccall, _c_rows = _corners_args(corners, n, nkv)                   # (_c_rows: the host array ccall points at, kept alive)
+        nbytes = lib.aid_processor_corners_workspace_bytes(C.byref(a), C.byref(ccall))
+    elif ep is not None:
         if seg_arr is not None:
             raise ValueError("an end-point store belongs to a self-attention call: no ip_segments")
         est = _endpoint_store_args(ep, s, c, x.dtype)
@@ -862,6 +870,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
                 _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
             elif kcall is not None:
                 _lib.check(kf_fwd(C.byref(a), C.byref(kcall), _stream()), kf_name)
+            elif ccall is not None:
+                _lib.check(lib.aid_processor_corners_fwd(C.byref(a), C.byref(ccall), _stream()), "aid_processor_corners_fwd")
             else:
                 _lib.check(lib.aid_processor_fwd(C.byref(a), _stream()), "aid_processor_fwd")
             raise RuntimeError("aid_processor_workspace_bytes returned 0")
@@ -871,6 +881,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
             _lib.check(lib.aid_processor_ep_fwd(C.byref(a), C.byref(est), _stream()), "aid_processor_ep_fwd")
         elif kcall is not None:
             _lib.check(kf_fwd(C.byref(a), C.byref(kcall), _stream()), kf_name)
+        elif ccall is not None:
+            _lib.check(lib.aid_processor_corners_fwd(C.byref(a), C.byref(ccall), _stream()), "aid_processor_corners_fwd")
         elif seg_arr is not None:
             _lib.check(lib.aid_processor_ip_fwd(C.byref(a), C.addressof(seg_arr), len(seg_arr), _stream()), "aid_processor_ip_fwd")
         else:
@@ -1083,3 +1095,123 @@ def processor_kf_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
     if kf.get("mode") == "replay" and plain:
         raise ValueError("key-frame stores replay into an interpolated (inner / outer) call")
     return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, kf=kf, **kwargs)
+
+
+# ---- corner-weighted AID (aid_hip.h: aid_mix_kv, aid_attn_corners_fwd, aid_processor_corners_fwd) ------------------------------------
+def _corners_args(corners: dict, n_frames: int, n_kv: int, scratch: Optional[torch.Tensor] = None):
+    """AidCorners of ``corners`` = dict(weights=float32 device [n_frames, M], rows=M ints) for a call of ``n_frames`` frames over ``n_kv``
+    rows of k / V^T (negative rows count from the end); returns (struct, the host row array it points at)."""
+    w = corners["weights"]
+    rows = [int(r) for r in corners["rows"]]
+    _require_gpu(w)
+    m = len(rows)
+    if not 1 <= m <= MAX_CORNERS:
+        raise ValueError(f"a call interpolates among 1 .. {MAX_CORNERS} corners; got {m}")
+    if w.dtype != torch.float32 or w.ndim != 2 or tuple(w.shape) != (n_frames, m) or not w.is_contiguous():
+        raise ValueError(f"weights must be a contiguous float32 device tensor [{n_frames}, {m}] (one row per frame, one column per corner); "
+                         f"got {tuple(w.shape)} {w.dtype}")
+    for r in rows:
+        if not -n_kv <= r < n_kv:
+            raise ValueError(f"corner row {r} outside the {n_kv} rows of k / V^T")
+    arr = (C.c_int32 * m)(*[r % n_kv for r in rows])
+    c = AidCorners()
+    c.rows, c.weights, c.n_corners = arr, w.data_ptr(), m
+    if scratch is not None:
+        c.scratch, c.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    return c, arr
+
+
+def mix_kv(k: torch.Tensor, vt: torch.Tensor, weights: torch.Tensor, rows: Sequence[int], n_plain: int = 0,
+           out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``k2[i] = sum_m weights[i, m] k[rows[m]]`` (and vt -> vt2) for the first ``N - n_plain`` frames in one streaming launch
+    (``aid_mix_kv``): k [F, L, C], vt [F, C, Lp] contiguous, ``weights`` float32 device [N, M] with M = len(rows) <= 8.  fp32 products
+    and sum in corner order, one rounding; a one-hot row returns the corner's bits.  Returns (k2 [N, L, C], vt2 [N, C, Lp]) — ``out``
+    or fresh tensors; the rows of the last ``n_plain`` frames are not written."""
+    dev = _require_gpu(k, vt, weights, *(out or ()))
+    dt = _dtype_code(k)
+    if k.dtype != vt.dtype or k.ndim != 3 or vt.ndim != 3 or not k.is_contiguous() or not vt.is_contiguous() or k.shape[0] != vt.shape[0]:
+        raise ValueError("k [F, L, C] and vt [F, C, Lp] must be contiguous tensors of one dtype with the same number of rows")
+    if weights.ndim != 2:
+        raise ValueError("weights must be [N, M]")
+    n = weights.shape[0]
+    cn, _rows = _corners_args(dict(weights=weights, rows=rows), n, k.shape[0])
+    if out is None:
+        out = (torch.empty(n, *k.shape[1:], dtype=k.dtype, device=k.device), torch.empty(n, *vt.shape[1:], dtype=k.dtype, device=k.device))
+    k2, vt2 = out
+    if k2.dtype != k.dtype or vt2.dtype != k.dtype or tuple(k2.shape) != (n, *k.shape[1:]) or tuple(vt2.shape) != (n, *vt.shape[1:]) \
+            or not k2.is_contiguous() or not vt2.is_contiguous():
+        raise ValueError("out must be (k2 [N, L, C], vt2 [N, C, Lp]) contiguous, laid out like k / vt")
+    with _on(dev):
+        _lib.check(_lib.load().aid_mix_kv(k.data_ptr(), vt.data_ptr(), k2.data_ptr(), vt2.data_ptr(), _rows, weights.data_ptr(), n,
+                                          int(n_plain), cn.n_corners, k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2], dt, _stream()),
+                   "aid_mix_kv")
+    return k2, vt2
+
+
+def attn_corners_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, *, l: int, weights: torch.Tensor,
+                     rows: Sequence[int], mode: str = "outer", fused: bool = False, n_plain: int = 0,
+                     out: Optional[torch.Tensor] = None, kv_map: Optional[torch.Tensor] = None,
+                     softmax_scale: Optional[float] = None, q_prescaled: bool = False, bias: Optional[torch.Tensor] = None,
+                     f32_attn_precision: Optional[str] = None) -> torch.Tensor:
+    """The attention core among up to 8 corners (``aid_attn_corners_fwd``): frame i has the non-negative weight row ``weights[i]``
+    (float32 device [N, M]) over the corner rows ``rows`` of k / vt,
+        outer:  O_i = sum_m w[i, m] A(Q_i, [K_i ;] K[r_m], ..)        inner:  O_i = A(Q_i, [K_i ;] sum_m w[i, m] K[r_m], ..)
+    The last ``n_plain`` frames run plain attention (their weight rows are not read).  Outer runs ceil(M / 2) passes of ``attn_fwd``
+    (the later ones accumulate, each rounding ``out`` once more); inner one ``mix_kv`` and one pass.  Tensors as ``attn_fwd``; with
+    ``kv_map`` the corner rows are rows of k / vt (context rows) and inner mixes one row per frame."""
+    lib = _lib.load()
+    attn_split = f32_attn_split_code(f32_attn_precision)
+    dev = _require_gpu(q, k, vt, out, weights, kv_map, bias)
+    dt = _dtype_code(q)
+    if _dtype_code(k) != dt or _dtype_code(vt) != dt:
+        raise TypeError("q, k, vt must share one dtype")
+    if mode not in ("inner", "outer"):
+        raise ValueError("a corner-weighted call is mode='inner' or 'outer'")
+    assert q.is_contiguous() and k.is_contiguous() and vt.is_contiguous()
+    n, s, c = q.shape
+    f = k.shape[0]
+    d = c // heads
+    if out is None:
+        out = torch.empty_like(q)
+    if kv_map is not None and (kv_map.dtype != torch.int32 or kv_map.numel() != n):
+        raise ValueError("kv_map must be an int32 device tensor with one entry per frame")
+    nb = int(lib.aid_corners_scratch_bytes(n, len(list(rows))))
+    scratch = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    cn, _rows = _corners_args(dict(weights=weights, rows=rows), n, f, scratch)
+    a = AidAttnArgs()
+    a.q, a.k, a.vt, a.out = q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr()
+    a.kv_map = _ptr(kv_map)
+    if mode == "inner":
+        k2 = torch.empty(n, *k.shape[1:], dtype=k.dtype, device=k.device)
+        vt2 = torch.empty(n, *vt.shape[1:], dtype=k.dtype, device=k.device)
+        a.k2, a.vt2 = k2.data_ptr(), vt2.data_ptr()
+    a.n_frames, a.n_kv = n, f
+    a.s, a.l, a.heads, a.d = s, l, heads, d
+    a.ldq, a.ldk, a.ldvt, a.ldo = c, k.shape[2], vt.shape[2], out.shape[2]
+    a.q_fs, a.k_fs, a.vt_fs, a.o_fs = s * c, k.shape[1] * k.shape[2], vt.shape[1] * vt.shape[2], s * out.shape[2]
+    a.mode, a.fused, a.dtype = MODES[mode], int(bool(fused)), dt
+    a.softmax_scale = float(d ** -0.5 if softmax_scale is None else softmax_scale)
+    a.n_plain = int(n_plain)
+    if bias is not None:
+        a.bias = bias.data_ptr()
+        a.bias_fs, a.bias_hs, a.bias_rs = score_bias_layout(bias, n, heads, s, l, q.dtype)
+    a.q_prescaled = int(bool(q_prescaled))
+    if dt == DTYPE_F32:
+        a.f32_split = attn_split
+    with _on(dev):
+        _lib.check(lib.aid_attn_corners_fwd(C.byref(a), C.byref(cn), _stream()), "aid_attn_corners_fwd")
+    return out
+
+
+def processor_corners_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,
+                          wo: torch.Tensor, bo: Optional[torch.Tensor], heads: int, *, weights: torch.Tensor, rows: Sequence[int],
+                          **kwargs) -> torch.Tensor:
+    """One whole processor call among up to 8 corners (``aid_processor_corners_fwd``) — still one library call: ``processor_fwd`` with
+    its attention step replaced by ``attn_corners_fwd``'s composition.  ``weights`` float32 device [N, M], ``rows`` the M corner rows of
+    k / V^T (frame rows, or context rows with ``ctx_map``); every other keyword is ``processor_fwd``'s (mode="inner" | "outer", fused,
+    n_plain, ctx_map, ln, residual, kv_cached, attn_bias, lora, f32_precision, ...) except ``coef`` / ``begin`` / ``end``, which a
+    corner-weighted call does not read, and the image branches and stores, which it does not take."""
+    for name in ("coef", "begin", "end", "ip", "ip_segments", "ep", "kf"):
+        if kwargs.get(name) is not None:
+            raise ValueError(f"a corner-weighted call takes no {name}=")
+    return processor_fwd(x, ctx, wq, wk, wv, wo, bo, heads, corners=dict(weights=weights, rows=rows), **kwargs)

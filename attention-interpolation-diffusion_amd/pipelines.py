@@ -46,10 +46,11 @@ from . import ops
 from . import processors as P
 from ._lib import KF_MAX_ROWS
 from .attn_shim import AttnStackUNet
-from .interp import generate_beta_tensor, linear_interpolation, slerp, spherical_interpolation
+from .interp import (corner_rows_of, generate_beta_tensor, linear_interpolation, nested_slerp, slerp,
+                     spherical_interpolation)
 from .endpoint_store import EndpointStore, run_settings, run_signature
 from .keyframe_store import KeyframePair, KeyframeStore
-from .loop import EARLY_MODES, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store, set_keyframe_store
+from .loop import EARLY_MODES, install_corner_processors, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store, set_keyframe_store
 from .sequence import SequenceBatch, prepare_sequence, prepare_single
 
 
@@ -786,6 +787,121 @@ class InterpolationStableDiffusionPipeline:
             set_ctx_index(self.unet, None)
             self.unet.set_attn_processor(installed)
         return self._decode(lat, output_type)
+
+    # -- corner-weighted interpolation among up to eight end points ----------------------
+    @torch.no_grad()
+    def interpolate_corners(self, latents, prompts: Optional[Sequence[str]] = None, weights=None,
+                            embeds: Optional[Sequence[tuple]] = None, guide_prompt: Optional[str] = None, embeds_guide=None,
+                            negative_prompt: Optional[str] = None, early: str = "fused_outer", late: str = "self",
+                            warmup_ratio: float = 0.5, num_inference_steps: int = 50, timesteps: Optional[List[int]] = None,
+                            sigmas: Optional[List[float]] = None, eta: float = 0.0, guidance_scale: Optional[float] = None,
+                            guidance_rescale: float = 0.0, generator=None, frame_latents: Optional[torch.Tensor] = None,
+                            use_graphs: Optional[bool] = None, output_type: str = "pil", **image_inputs):
+        """Build-specific: N frames interpolated among M <= 8 end points ("corners") in one run — a 2 x 2 morph grid between four
+        prompts or seeds (``grid_weights``), a prompt with three components (``simplex_weights``).  ``latents`` [M, C, h, w] (or M
+        tensors [1, C, h, w]) and ``prompts`` / ``embeds`` (one per corner, as ``interpolate`` takes ``prompt_start`` /
+        ``embeds_start``) describe the corners; ``weights`` [N, M] the frames: rows non-negative, summing to 1 within 1e-6, and for
+        every corner a frame whose row is exactly one-hot — that frame IS the corner (``corner_rows[m]``, the first such frame), the
+        corner frames sit in the batch as the two end points of ``interpolate`` do.  Anything else raises ``ValueError`` naming the row.
+        Frame latents: ``nested_slerp`` of the corner latents in corner order (``slerp(x_0, x_1, c)`` for M = 2), or ``frame_latents``
+        [N, C, h, w].  Conditional, negative (and SDXL pooled) embeddings of a frame: the weight-mixed corner embeddings; with a guide
+        prompt every frame that is not a corner takes the guide's, shared through ``ctx_index`` as in ``interpolate``.  The two
+        passes of a step run as one UNet call ``[cond N ; uncond N]``, the second half as plain riders.  ``early`` / ``late`` /
+        ``warmup_ratio`` / ``timesteps`` / ``sigmas`` / ``eta`` / ``generator`` / ``guidance_rescale`` / ``use_graphs`` as in
+        ``interpolate_single`` and ``interpolate``.  IP-Adapter image inputs raise ``NotImplementedError``."""
+        for name in image_inputs:
+            if name in ("image_start", "image_end", "image_embeds_start", "image_embeds_end", "images", "image_embeds",
+                        "ip_adapter_image", "ip_adapter_image_embeds"):
+                raise NotImplementedError(f"interpolate_corners takes no image inputs ({name}): the IP-Adapter image branches "
+                                          "interpolate between two end points only")
+            raise TypeError(f"interpolate_corners() got an unexpected keyword argument {name!r}")
+        if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
+            raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
+        lats = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
+        m = len(lats)
+        w, corner_rows = corner_rows_of(weights, m)
+        n = w.shape[0]
+        for what, seq in (("prompts", prompts), ("embeds", embeds)):
+            if seq is not None and len(seq) != m:
+                raise ValueError(f"interpolate_corners needs one entry of {what} per corner: {len(seq)} for {m} corners")
+        gs = self.default_guidance_scale if guidance_scale is None else guidance_scale
+        gr = _check_rescale(guidance_rescale)
+        self._guidance_scale, self._guidance_rescale = gs, gr
+        dev, dtype = self._unet_device_dtype()
+        sides = [self._split(self._embed(None if prompts is None else prompts[i], negative_prompt,
+                                         None if embeds is None else embeds[i])) for i in range(m)]
+        guide = None
+        if guide_prompt is not None or embeds_guide is not None:
+            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide))
+        onehot = [int(torch.nonzero(w[i] == 1.0)[0]) if bool((w[i] == 1.0).any()) and int((w[i] != 0).sum()) == 1 else None
+                  for i in range(n)]
+
+        def mixed(slot: int, side: int):
+            """[N, ...]: corner tensors ``sides[.][side][slot]`` mixed with the weight rows (a one-hot row takes its corner's bits)."""
+            src = [sides[c][side][slot] for c in range(m)]
+            acc = torch.float64 if src[0].dtype == torch.float64 else torch.float32
+            stack = torch.cat([t_.to(acc) for t_ in src], dim=0)
+            rows = []
+            for i in range(n):
+                if onehot[i] is not None:
+                    rows.append(src[onehot[i]])
+                else:
+                    rows.append(torch.tensordot(w[i].to(stack.device, acc), stack, dims=1).unsqueeze(0).to(src[0].dtype))
+            return torch.cat(rows, dim=0)
+
+        idx = None
+        if guide is not None and any(o is None for o in onehot):
+            # one context row per frame, as interpolate hands them over; ctx_index names the distinct ones — the M corners', then the
+            # guide's, which every frame that is not a corner shares (its keys / values are projected once)
+            cond = torch.cat([guide[0][0] if o is None else sides[o][0][0] for o in onehot], dim=0)
+            unc = torch.cat([guide[1][0] if o is None else sides[o][1][0] for o in onehot], dim=0)
+            idx = [m if o is None else o for o in onehot]
+            pooled = None
+            if len(sides[0][0]) > 1:
+                pooled = tuple(torch.cat([(guide[s_][1] if o is None else sides[o][s_][1]) for o in onehot], dim=0) for s_ in (0, 1))
+        else:
+            cond, unc = mixed(0, 0), mixed(0, 1)
+            pooled = (mixed(1, 0), mixed(1, 1)) if len(sides[0][0]) > 1 else None
+        n_distinct = m + 1
+        cond, unc = cond.to(dev, dtype), unc.to(dev, dtype)
+        if frame_latents is not None:
+            if tuple(frame_latents.shape) != (n,) + tuple(lats[0].shape[1:]):
+                raise ValueError(f"frame_latents must be [{n}, ...] like the corner latents; got {tuple(frame_latents.shape)}")
+            lat = frame_latents.to(dev, dtype)
+        else:
+            cl = [l_.to(dev, dtype) for l_ in lats]
+            lat = torch.cat([nested_slerp(cl, w[i]) for i in range(n)], dim=0)
+        _, num_inference_steps = _retrieve_timesteps(self.scheduler, num_inference_steps, dev, timesteps, sigmas)
+        extra_step_kwargs = _extra_step_kwargs(self.scheduler, eta, generator)
+        warmup_steps = int(num_inference_steps * warmup_ratio)
+        installed = dict(self.unet.attn_processors)
+        try:
+            procs = {}
+            for mode in {early} | ({late} - {"self"}):
+                install_corner_processors(self.unet, w, corner_rows, early=mode)
+                procs[mode] = dict(self.unet.attn_processors)
+            graphs = _PassGraphs(_use_graphs(use_graphs, dev))
+            ctx_both = torch.cat([cond, unc])               # ONE tensor for the whole run: the text K / V cache keys on it
+            added_both = self._added_cond(None if pooled is None else torch.cat(pooled), 2 * n)
+            idx_both = None if idx is None else idx + [j + n_distinct for j in idx]
+
+            def both_pass(x, t):
+                return self._unet(torch.cat([x, x]), t, ctx_both, added_both)
+
+            for i, t in enumerate(self.scheduler.timesteps):
+                x = self.scheduler.scale_model_input(lat, t)
+                td = _dev_scalar(t, dev) if graphs.enabled else t
+                mode = early if i < warmup_steps else late
+                self.unet.set_attn_processor(procs[mode] if mode != "self" else procs[early])
+                set_aid_active(self.unet, mode != "self", plain_tail=n if mode != "self" else 0)
+                set_ctx_index(self.unet, idx_both)
+                both = graphs.run(("both", mode), both_pass, x=x, t=td)
+                noise = _guided_noise(both[:n], both[n:], gs, gr)
+                lat = self.scheduler.step(noise, t, lat, **extra_step_kwargs, return_dict=False)[0]
+        finally:
+            set_ctx_index(self.unet, None)
+            self.unet.set_attn_processor(installed)
+        return self._decode(lat, "latent" if output_type == "latent" else ("np" if output_type in ("pil", "np") else output_type))
 
     # -- key frames: record once, render between any two (DESIGN.md §3.6d) --------------------------------
     @torch.no_grad()

@@ -636,6 +636,141 @@ class InnerInterpolatedAttnProcessor(InterpolatedAttnProcessor):
         return _run_text(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, "inner", ctx_index)
 
 
+class CornerInterpolatedAttnProcessor(InterpolatedAttnProcessor):
+    r"""Build-specific: AID among up to eight end points ("corners").  Frame i of the batch has a row of
+    non-negative weights ``weights[i]`` over the M corner frames ``corner_rows`` (frames of the same batch, as the two end points are):
+        outer:  \sum_m w_{im} A(Q_i, [K_i,] K_{r_m}, [V_i,] V_{r_m})        inner:  A(Q_i, [K_i,] \sum_m w_{im} K_{r_m}, [V_i,] ...)
+    M = 2 with rows ``(1 - t, t)`` is the outer / inner processor above.  ``weights`` is a CPU tensor attribute ``[size, M]`` like
+    ``coef``: assigning it, or editing it in place, rewrites the device buffers in place (a captured graph reads live values; a change
+    inside a stream capture raises).  ``plain_tail``, ``ctx_index`` (a corner's context row is ``ctx_index[corner_rows[m]]``),
+    ``activated`` / ``deactivate()`` as on the text processors; one library call per layer (``ops.processor_corners_fwd``).
+    No IP-Adapter layers, no stores, no end-point exchange."""
+    _mode = "corners"
+
+    def __init__(self, weights, corner_rows: Sequence[int], mode: str = "outer", is_fused: bool = True, original_attn=None):
+        if mode not in ("outer", "inner"):
+            raise ValueError(f"mode must be 'outer' or 'inner'; got {mode!r}")
+        w = _check_corner_weights(weights, corner_rows)
+        super().__init__(size=max(w.shape[0], 2), is_fused=is_fused)
+        self._w_dev: Dict[Tuple, list] = {}
+        self.size = w.shape[0]
+        self.mode = mode
+        self.corner_rows = [int(r) for r in corner_rows]
+        self.original_attn = original_attn
+        self.weights = w
+        self.coef = torch.zeros(self.size)           # (not read by a corner call; sized like the batch for code that inspects it)
+
+    @property
+    def weights(self) -> torch.Tensor:
+        return self._weights
+
+    @weights.setter
+    def weights(self, value) -> None:
+        w = _check_corner_weights(value, self.corner_rows)
+        if w.shape[0] != self.size:
+            raise ValueError(f"weights has {w.shape[0]} rows; the processor holds {self.size} frames")
+        self._weights = w
+        for (device, tail), ent in self._w_dev.items():
+            _rewrite(ent, _corner_values(w, tail), _version_of(w))
+
+    def activate(self, t=None):
+        """Unlike the two-end-point processors there is no coefficient to set: the weights stay."""
+        self.activated = True
+
+    def _weights_device(self, device: torch.device, batch: int) -> torch.Tensor:
+        """The weight rows as float32 ``[size + plain_tail, M]`` on ``device`` (the riders' rows are zero and never read), allocated
+        once per (device, plain_tail) and rewritten in place from then on."""
+        w = self._weights
+        if w.shape[0] + self.plain_tail != batch:
+            raise RuntimeError(f"The size of tensor a ({w.shape[0] + self.plain_tail}) must match the size of "
+                               f"tensor b ({batch}) at non-singleton dimension 0")
+        key = (device, self.plain_tail)
+        ent = self._w_dev.get(key)
+        ver = _version_of(w)
+        if ent is None:
+            vals = _corner_values(_check_corner_weights(w, self.corner_rows), self.plain_tail)
+            ent = [torch.tensor(vals, dtype=torch.float32).to(device), vals, ver]
+            self._w_dev[key] = ent
+        elif ver is None or ent[2] != ver:            # edited in place (proc.weights[1, 0] = ...)
+            _rewrite(ent, _corner_values(_check_corner_weights(w, self.corner_rows), self.plain_tail), ver)
+        return ent[0]
+
+    def fused_sublayer(self, attn, norm, hidden_states, encoder_hidden_states=None, ctx_index=None):
+        foreign = (not self.activated) and self.original_attn is not None and not isinstance(self.original_attn, HipAttnProcessor)
+        if foreign or not _plain_sublayer_ok(attn, hidden_states) or isinstance(encoder_hidden_states, tuple):
+            return hidden_states + self(attn, norm(hidden_states), encoder_hidden_states, ctx_index=ctx_index)
+        ctx_index = self.ctx_index if ctx_index is None else ctx_index
+        hidden_states = hidden_states.contiguous()
+        kw = dict(ln=_ln_of(norm), add_to=hidden_states, ln_folded=_ln_folded(attn, norm, encoder_hidden_states is not None))
+        if not self.activated:
+            return _run_text(self, attn, hidden_states, encoder_hidden_states, None, None, "plain", ctx_index, **kw)
+        return _run_corners(self, attn, hidden_states, encoder_hidden_states, None, None, ctx_index, **kw)
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, ctx_index=None):
+        ctx_index = self.ctx_index if ctx_index is None else ctx_index
+        if not self.activated:
+            if self.original_attn is not None:
+                if ctx_index is not None:
+                    return self.original_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index=ctx_index)
+                return self.original_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+            return _run_text(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, "plain", ctx_index)
+        return _run_corners(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index)
+
+
+def _check_corner_weights(weights, corner_rows) -> torch.Tensor:
+    """``weights`` as a float32 CPU tensor [size, M] (the caller's tensor itself where it is one, so in-place edits are seen):
+    M = len(corner_rows) in 1 .. 8, finite non-negative entries, every corner row a frame of the batch."""
+    w = weights if torch.is_tensor(weights) else torch.as_tensor(weights, dtype=torch.float32)
+    if w.is_cuda or w.dtype != torch.float32:
+        w = w.detach().to("cpu", torch.float32)
+    rows = [int(r) for r in corner_rows]
+    if w.ndim != 2 or not 1 <= w.shape[1] <= ops.MAX_CORNERS or w.shape[1] != len(rows) or w.shape[0] < 1:
+        raise ValueError(f"weights must be [size, M] with M = len(corner_rows) in 1 .. {ops.MAX_CORNERS}; got {tuple(w.shape)} for "
+                         f"{len(rows)} corner rows")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("corner weights must be finite and non-negative")
+    for r in rows:
+        if not 0 <= r < w.shape[0]:
+            raise ValueError(f"corner row {r} is not a frame of the batch (0 .. {w.shape[0] - 1})")
+    return w
+
+
+def _corner_values(w: torch.Tensor, plain_tail: int) -> Tuple[Tuple[float, ...], ...]:
+    """Host values of a device weight buffer: the rows of ``w``, then ``plain_tail`` rows of zeros (never read: aid_hip.h)."""
+    return tuple(tuple(r) for r in w.detach().tolist()) + ((0.0,) * w.shape[1],) * plain_tail
+
+
+def _run_corners(proc: CornerInterpolatedAttnProcessor, attn, hidden_states, encoder_hidden_states, attention_mask, temb,
+                 ctx_index=None, ln=None, add_to=None, ln_folded=None):
+    """``_run_text`` for a corner-weighted call: the same prologue, context sharing, text K / V cache, LoRA operands and epilogue around
+    ``ops.processor_corners_fwd``."""
+    if isinstance(encoder_hidden_states, tuple):
+        raise NotImplementedError("CornerInterpolatedAttnProcessor on an IP-Adapter layer ((text, [image_embeds]) contexts): the "
+                                  "image branches interpolate between two end points only")
+    for name, what in (("endpoint_store", "an end-point store"), ("keyframe_store", "a key-frame store"),
+                       ("endpoint_exchange", "endpoint_exchange")):
+        if getattr(proc, name, None) is not None:
+            raise NotImplementedError(f"{what} with corner weights: the stores and the exchange hold two end points")
+    residual, x, ctx, shape4, mask = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+    ehs = ctx
+    wq, wk, wv, wo, bo = _weights(attn)
+    bias = _score_bias(mask, x, x.shape[1] if ctx is None else ctx.shape[1], proc.is_fused, type(proc).__name__)
+    w_dev = proc._weights_device(x.device, x.shape[0])
+    rows = list(proc.corner_rows)
+    ctx_map = idx = None
+    ctx_index = proc.ctx_index if ctx_index is None else ctx_index
+    if ctx is not None and ctx_index is not None:
+        ctx, ctx_map, idx = _shared_context(proc._ctx_cache, ctx_index, ctx, x.shape[0])
+        rows = [idx[r] for r in rows]                 # corner rows of the key / value tensors
+    elif ctx is not None:
+        ctx = ctx.contiguous()
+    kv, la = _kv_and_lora(attn, ehs, ctx, idx, wk, wv, x)
+    y = ops.processor_corners_fwd(x, ctx, wq, wk, wv, wo, bo, attn.heads, weights=w_dev, rows=rows, mode=proc.mode,
+                                  fused=proc.is_fused, ctx_map=ctx_map, n_plain=proc.plain_tail, ln=ln, residual=add_to,
+                                  ln_folded=ln_folded, kv_cached=kv, attn_bias=bias, lora=la)
+    return _epilogue(attn, y, residual, shape4)
+
+
 # ---------------------------------------------------------------------------------------------
 # IP-Adapter variants.  The reference hard-wires a batch of 3 (literal ``expand(3, ...)``, ``[::3]``, ``[6:9]``;
 # SURVEY.md App. D5).  Here the batch is ``coef.numel()`` frames and the image-embedding tensor ``[R, 1, T, Cc]`` holds

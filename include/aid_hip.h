@@ -672,6 +672,68 @@ size_t aid_processor_kf_q8_workspace_bytes(const AidProcessorArgs* args /* host 
 int    aid_processor_kf_q8_fwd(const AidProcessorArgs* args /* host */, const AidKeyframeCall* kf /* host */, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Corner-weighted AID: interpolation among up to AID_MAX_CORNERS end points, in the LIVE form — the corner frames sit in the batch, as
+ * the two end points of aid_attn_fwd do (no ABI version change: five new entry points, no existing struct, constant or entry point
+ * changes; no stores).  Corners are rows r_0 .. r_{M-1} of k / vt (frame rows, or context rows when kv_map / ctx_map is given;
+ * duplicates allowed), 1 <= M <= AID_MAX_CORNERS.  Frame i has an fp32 weight row w[i, 0 .. M), non-negative, in a DEVICE tensor
+ * [n_frames, M] read by the kernels, like the coefficient buffers: a captured graph reads live values.
+ *   OUTER : O_i = sum_m w[i, m] * A(Q_i, [K_i ;] K[r_m], [V_i ;] V[r_m])
+ *   INNER : Kc_i = sum_m w[i, m] * K[r_m]   (same for V);   O_i = A(Q_i, [K_i ;] Kc_i, [V_i ;] Vc_i)
+ * with [K_i ;] present when `fused` and A as in aid_attn_fwd.  The last n_plain frames of a call are PLAIN riders (O_i = A(Q_i, K_i, V_i));
+ * here n_plain is AUTHORITATIVE and the riders' weight rows are not read.  M = 2 with w = (1 - c, c) is aid_attn_fwd's OUTER / INNER.
+ *
+ * aid_mix_kv — the INNER mix, one streaming launch:
+ *   k2[i] = sum_m w[i, m] * k[rows[m]]    vt2[i] = sum_m w[i, m] * vt[rows[m]]       for i in [0, n_frames - n_plain)
+ * Products and sum in fp32, in corner order, one rounding to the storage type; a term with weight exactly 0 is skipped, so a one-hot
+ * row returns the corner's bits (f32 storage carries the rounding errors of the sum along and adds them before the final rounding).
+ * k_fs / vt_fs are the row strides in elements of all four tensors.  Reads exactly k[rows[m] * k_fs .. + k_fs) and
+ * vt[rows[m] * vt_fs .. + vt_fs) for every m — each ONCE per launch, whatever n_frames is — and w[i, 0 .. M) for i < n_frames - n_plain.
+ * Writes exactly k2[i * k_fs .. + k_fs) and vt2[i * vt_fs .. + vt_fs) for i < n_frames - n_plain: the whole stride of a mixed frame,
+ * gap rows and V^T pad columns included, mixed from whatever k / vt hold there, exactly as aid_lerp_kv does; the riders' rows of
+ * k2 / vt2 are untouched.  `rows` is a HOST array (its entries travel by value in the kernel arguments).
+ * AID_ERR_ARG: a NULL pointer, n_corners outside 1 .. AID_MAX_CORNERS, a negative row, n_frames < 1, n_plain outside [0, n_frames];
+ * AID_ERR_SHAPE: k_fs / vt_fs not positive multiples of 8, k / vt / k2 / vt2 not 16-byte aligned, weights not 4-byte aligned;
+ * AID_ERR_DTYPE — all before any launch.  16-byte vector loads and stores on a grid-stride walk; no LDS, no atomics.
+ *
+ * aid_attn_corners_fwd — aid_attn_fwd among the corners.  AidAttnArgs is unchanged; its coef, begin, end, frame_scale, accumulate and
+ * out_scale are NOT read, mode is AID_MODE_INNER or AID_MODE_OUTER (PLAIN: AID_ERR_ARG).  One small launch first fills the PAIR TABLE
+ * in `scratch` (caller-owned device memory, 16-byte aligned, aid_corners_scratch_bytes(n_frames, n_corners) bytes; too small:
+ * AID_ERR_WORKSPACE) from the weights: for pass p = 0 .. ceil(M / 2) - 1, with a = w[i, 2p], b = (2p + 1 < M) ? w[i, 2p + 1] : 0,
+ * s = a + b:   coef_p[i] = s > 0 ? b / s : 0,   scale_p[i] = s;   riders: coef = -1, scale = 1   (no division by zero, no NaN).
+ *   INNER  aid_mix_kv into the caller's k2 / vt2, then ONE aid_attn_fwd whose coefficient is 0.5 for every AID frame and -1 for the
+ *          riders: every AID frame reads its k2 / vt2 row.
+ *   OUTER  pass 0 is aid_attn_fwd over all frames with begin = r_0, end = r_1 (r_0 when M = 1), coef_0, frame_scale = scale_0,
+ *          accumulate = 0; pass p >= 1 runs over the first n_frames - n_plain frames with begin = r_2p, end = r_2p+1, coef_p,
+ *          frame_scale = scale_p, accumulate = 1.  A lone last corner is the pair (r, r) with coefficient 0.  Each accumulating pass
+ *          rounds `out` once more in its storage type.
+ * Every refusal of aid_attn_fwd applies (a `bias` with `fused` included); a corner row >= n_kv, n_plain outside [0, n_frames] and
+ * every NULL pointer of AidCorners is AID_ERR_ARG; weights not 4-byte / scratch not 16-byte aligned AID_ERR_SHAPE — all before any launch.
+ *
+ * aid_processor_corners_fwd — aid_processor_fwd with its attention step replaced by that composition; the pair table (and, for
+ * INNER, k2 / vt2) are carved from the workspace, which must hold aid_processor_corners_workspace_bytes() bytes
+ * (AidCorners.scratch is not read).  args->coef / begin / end are not read.  corners == NULL is aid_processor_fwd.  mode == PLAIN,
+ * ip != NULL, a corner row >= the number of k / V^T rows: AID_ERR_ARG, with everything aid_processor_fwd checks, before the first
+ * launch.  LoRA / DoRA, LayerNorm (folded or not), residual, f32_split / f32_attn_split, attn_bias (not with fused) and cached text
+ * K / V work as in aid_processor_fwd: it is the same code path.
+ * ------------------------------------------------------------------------------------- */
+#define AID_MAX_CORNERS 8
+
+typedef struct AidCorners {
+    const int32_t* rows;         /* HOST: n_corners rows of k / vt                             */
+    const float*   weights;      /* DEVICE fp32 [n_frames, n_corners], read by the kernels     */
+    void*          scratch;      /* DEVICE: the pair table (aid_attn_corners_fwd only)         */
+    size_t         scratch_bytes;
+    int32_t        n_corners;    /* 1 .. AID_MAX_CORNERS                                       */
+} AidCorners;
+
+int    aid_mix_kv(const void* k, const void* vt, void* k2, void* vt2, const int32_t* rows /* host */, const float* weights /* device */,
+                  int32_t n_frames, int32_t n_plain, int32_t n_corners, int64_t k_fs, int64_t vt_fs, int32_t dtype, void* stream);
+size_t aid_corners_scratch_bytes(int32_t n_frames, int32_t n_corners);      /* 0 for n_frames < 1 or n_corners outside 1 .. 8 */
+int    aid_attn_corners_fwd(const AidAttnArgs* args /* host */, const AidCorners* corners /* host */, void* stream);
+size_t aid_processor_corners_workspace_bytes(const AidProcessorArgs* args /* host */, const AidCorners* corners /* host */);
+int    aid_processor_corners_fwd(const AidProcessorArgs* args /* host */, const AidCorners* corners /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
