@@ -13,14 +13,14 @@ interpolate_single / N-frame interpolate)  ·  endpoint_store.py (recorded end p
 """
 from .interp import (generate_beta_tensor, grid_weights, linear_interpolation, nested_slerp, simplex_weights, slerp,
                      spherical_interpolation)
-from .processors import (CornerInterpolatedAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
+from .processors import (CornerInterpolatedAttnProcessor, KeyframeBlendAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
                          InnerInterpolatedIPAttnProcessor, InterpolatedAttnProcessor, OuterInterpolatedAttnProcessor,
                          OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, activate_aid,
                          clear_text_kv_cache, clear_weight_caches, deactivate_aid, load_aid, load_aid_ip_adapter)
 from .attn_shim import AttnShim, AttnStackUNet, IPAdapterShim
 from . import ops, _lib, sequence, loop, dist, prior, pipelines, endpoint_store, keyframe_store
 from .endpoint_store import EndpointStore
-from .keyframe_store import KeyframeStore
+from .keyframe_store import KeyframeBlend, KeyframeStore
 from .ops import get_f32_attn_precision, set_f32_attn_precision
 from .prior import BetaPriorExplorer, BetaPriorPipeline
 from .pipelines import (DDIMSchedulerLite, InterpolationStableDiffusionPipeline,
@@ -28,13 +28,13 @@ from .pipelines import (DDIMSchedulerLite, InterpolationStableDiffusionPipeline,
 
 __all__ = [
     "generate_beta_tensor", "linear_interpolation", "slerp", "spherical_interpolation", "grid_weights", "simplex_weights", "nested_slerp",
-    "CornerInterpolatedAttnProcessor",
+    "CornerInterpolatedAttnProcessor", "KeyframeBlendAttnProcessor",
     "InterpolatedAttnProcessor", "OuterInterpolatedAttnProcessor", "InnerInterpolatedAttnProcessor",
     "OuterInterpolatedIPAttnProcessor", "InnerInterpolatedIPAttnProcessor", "ScaleControlIPAttnProcessor",
     "HipAttnProcessor", "HipIPAdapterAttnProcessor", "load_aid", "load_aid_ip_adapter", "activate_aid", "deactivate_aid",
     "clear_text_kv_cache", "clear_weight_caches",
     "AttnShim", "AttnStackUNet", "IPAdapterShim", "ops", "set_f32_attn_precision", "get_f32_attn_precision",
     "BetaPriorPipeline", "BetaPriorExplorer", "InterpolationStableDiffusionPipeline", "InterpolationStableDiffusionXLPipeline", "DDIMSchedulerLite", "StackDenoiser",
-    "EndpointStore", "KeyframeStore",
+    "EndpointStore", "KeyframeStore", "KeyframeBlend",
 ]
 __version__ = "0.1.0"

@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "aid_keyframe_rows", "aid_processor_kf_workspace_bytes", "aid_processor_kf_fwd",
     "aid_q8_block_bytes", "aid_keyframe_rows_q8", "aid_processor_kf_q8_workspace_bytes", "aid_processor_kf_q8_fwd",
     "aid_mix_kv", "aid_corners_scratch_bytes", "aid_attn_corners_fwd", "aid_processor_corners_workspace_bytes", "aid_processor_corners_fwd",
+    "aid_mix_kv_stores", "aid_processor_kf_blend_workspace_bytes", "aid_processor_kf_blend_fwd",
     "aid_abi_version", "aid_strerror", "aid_last_attn_variant", "aid_last_gemm_variant", "aid_device_info",
     "aid_profile_begin", "aid_profile_end", "aid_set_tuning", "aid_get_tuning", "aid_stream_capture_id",
 )
@@ -169,6 +170,13 @@ class AidCorners(C.Structure):
     ]
 
 
+class AidKeyframeBlend(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(AidKeyframeRow)), ("step", C.c_void_p), ("weights", C.c_void_p),
+        ("n_corners", C.c_int32), ("n_steps", C.c_int32), ("q8", C.c_int32),
+    ]
+
+
 class AidProfileEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double),
                 ("flops_executed", C.c_double)]
@@ -273,6 +281,13 @@ def bind(path: str) -> C.CDLL:
     lib.aid_processor_corners_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidCorners)]
     lib.aid_processor_corners_fwd.restype = C.c_int
     lib.aid_processor_corners_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidCorners), C.c_void_p]
+    lib.aid_mix_kv_stores.restype = C.c_int
+    lib.aid_mix_kv_stores.argtypes = [C.POINTER(AidKeyframeBlend), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.aid_processor_kf_blend_workspace_bytes.restype = C.c_size_t
+    lib.aid_processor_kf_blend_workspace_bytes.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeBlend)]
+    lib.aid_processor_kf_blend_fwd.restype = C.c_int
+    lib.aid_processor_kf_blend_fwd.argtypes = [C.POINTER(AidProcessorArgs), C.POINTER(AidKeyframeBlend), C.c_void_p]
     lib.aid_set_tuning.restype = C.c_int
     lib.aid_set_tuning.argtypes = [C.c_char_p, C.c_int]
     lib.aid_get_tuning.restype = C.c_int

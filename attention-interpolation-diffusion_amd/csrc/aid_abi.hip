@@ -733,8 +733,65 @@ static AidAttnArgs corner_pass0(const AidAttnArgs& a, const AidCorners& c, const
     return at;
 }
 
+// ---- key-frame blend (aid_hip.h): the corners are block rows of key-frame stores ---------------------------------------------------
+// what is wrong with the AidKeyframeBlend itself, in two rounds so that a caller can keep the order ARG, DTYPE, SHAPE of every entry
+static int check_blend_arg(const AidKeyframeBlend* b, int n_frames, int n_plain) {
+    if (!b || !b->rows || !b->step || !b->weights || !aligned4(b->step)) return AID_ERR_ARG;
+    if (b->n_corners < 1 || b->n_corners > AID_MAX_CORNERS || b->n_steps < 1 || (b->q8 != 0 && b->q8 != 1)) return AID_ERR_ARG;
+    if (n_plain < 0 || n_plain > n_frames) return AID_ERR_ARG;
+    for (int m = 0; m < b->n_corners; ++m)
+        if (!b->rows[m].k_store || !b->rows[m].vt_store) return AID_ERR_ARG;
+    return AID_OK;
+}
+
+static int check_blend_shape(const AidKeyframeBlend& b) {
+    for (int m = 0; m < b.n_corners; ++m)
+        if (!aligned16(b.rows[m].k_store) || !aligned16(b.rows[m].vt_store)) return AID_ERR_SHAPE;
+    return aligned4(b.weights) ? AID_OK : AID_ERR_SHAPE;
+}
+
+static int check_mix_stores(const AidKeyframeBlend* b, const void* k2, const void* vt2, int32_t n_frames, int32_t n_plain, int64_t k_fs,
+                            int64_t vt_fs, int32_t vt_ld, int32_t vt_cols, int32_t dtype) {
+    if (!k2 || !vt2 || n_frames < 1) return AID_ERR_ARG;
+    const int rc = check_blend_arg(b, n_frames, n_plain);
+    if (rc != AID_OK) return rc;
+    if (!dtype_ok(dtype)) return AID_ERR_DTYPE;
+    if (k_fs < 8 || vt_fs < 8 || k_fs % 8 || vt_fs % 8) return AID_ERR_SHAPE;
+    if (b->q8 && (vt_ld < 8 || vt_ld % 8 || vt_fs % vt_ld || vt_cols < 1 || vt_cols > vt_ld)) return AID_ERR_SHAPE;
+    if (!aligned16(k2) || !aligned16(vt2)) return AID_ERR_SHAPE;
+    return check_blend_shape(*b);
+}
+
+static int mix_kv_stores_impl(const aid::MixStoresArgs& ms, void* stream) {
+    hipError_t e;
+    {
+        // traffic: block row *step of every store read once, one mixed row written per AID frame
+        const double es = ms.dtype == AID_DTYPE_F32 ? 4.0 : 2.0, elems = (double)(ms.k_fs + ms.vt_fs);
+        const double stored = ms.q8 ? (double)(ms.k_fs + (ms.k_fs + 31) / 32 + ms.vt_fs + (ms.vt_fs + 31) / 32) : es * elems;
+        char nm[64];
+        snprintf(nm, sizeof(nm), "aid_mix_kv_stores<%s,m%d,%s>", dtype_name(ms.dtype), ms.n_corners, ms.q8 ? "q8" : "native");
+        ProfScope ps(static_cast<hipStream_t>(stream), nm, 2.0 * ms.n_corners * ms.n_mix * elems,
+                     ms.n_corners * stored + es * ms.n_mix * elems);
+        e = aid::mix_kv_stores_launch(ms, static_cast<hipStream_t>(stream));
+    }
+    return e == hipSuccess ? AID_OK : fail_hip(e, "aid_mix_kv_stores");
+}
+
+int aid_mix_kv_stores(const AidKeyframeBlend* b, void* k2, void* vt2, int32_t n_frames, int32_t n_plain, int64_t k_fs, int64_t vt_fs,
+                      int32_t vt_ld, int32_t vt_cols, int32_t dtype, void* stream) {
+    const int rc = check_mix_stores(b, k2, vt2, n_frames, n_plain, k_fs, vt_fs, vt_ld, vt_cols, dtype);
+    if (rc != AID_OK) return rc;
+    aid::MixStoresArgs ms;
+    ms.rows = b->rows; ms.step = b->step; ms.weights = b->weights; ms.k2 = k2; ms.vt2 = vt2;
+    ms.n_corners = b->n_corners; ms.n_steps = b->n_steps; ms.q8 = b->q8; ms.n_mix = n_frames - n_plain;
+    ms.k_fs = k_fs; ms.vt_fs = vt_fs; ms.vt_ld = vt_ld; ms.vt_cols = vt_cols; ms.dtype = dtype;
+    return mix_kv_stores_impl(ms, stream);
+}
+
 // the composition over aid_attn_fwd (aid_hip.h); `a` and `c` are checked, tab = the pair table's memory
-static int attn_corners_impl(const AidAttnArgs& a, const AidCorners& c, float* tab, void* stream) {
+// mix_src (INNER only): the corners are key-frame stores — the mix reads them instead of rows c.rows of a.k / a.vt
+static int attn_corners_impl(const AidAttnArgs& a, const AidCorners& c, float* tab, void* stream,
+                             const aid::MixStoresArgs* mix_src = nullptr) {
     const int n = a.n_frames, n_mix = a.n_frames - a.n_plain, M = c.n_corners;
     hipError_t e;
     {
@@ -744,8 +801,9 @@ static int attn_corners_impl(const AidAttnArgs& a, const AidCorners& c, float* t
     if (e != hipSuccess) return fail_hip(e, "aid_attn_corners_fwd");
     AidAttnArgs at = corner_pass0(a, c, tab);
     if (a.mode == AID_MODE_INNER) {             // every AID frame reads its mixed row (coefficient 0.5), the riders their own keys
-        const int rc = mix_kv_impl(a.k, a.vt, const_cast<void*>(a.k2), const_cast<void*>(a.vt2), c.rows, c.weights, n, a.n_plain, M,
-                                   a.k_fs, a.vt_fs, a.dtype, stream);
+        const int rc = mix_src ? mix_kv_stores_impl(*mix_src, stream)
+                               : mix_kv_impl(a.k, a.vt, const_cast<void*>(a.k2), const_cast<void*>(a.vt2), c.rows, c.weights, n, a.n_plain,
+                                             M, a.k_fs, a.vt_fs, a.dtype, stream);
         if (rc != AID_OK) return rc;
         return aid_attn_fwd(&at, stream);
     }
@@ -907,7 +965,8 @@ static int check_keyframe_call(const AidProcessorArgs& a, const AidKeyframeCall&
 }
 
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream, bool kf_q8 = false, const AidCorners* cn = nullptr);
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8 = false, const AidCorners* cn = nullptr,
+                          const AidKeyframeBlend* kb = nullptr);
 
 size_t aid_processor_ep_workspace_bytes(const AidProcessorArgs* args, const AidEndpointStore* ep) {
     if (!args) return 0;
@@ -962,12 +1021,39 @@ int aid_processor_corners_fwd(const AidProcessorArgs* args, const AidCorners* co
     return processor_impl(args, nullptr, 0, nullptr, nullptr, stream, false, corners);
 }
 
+// The AidProcessorArgs a key-frame blend call is checked and carved with: a self-attention AID call over the local frames; as for a
+// corner call the weights stand in for coef, and no end point is a row of the call (begin = end = 0).  Everything but the alignment
+// rules of the AidKeyframeBlend (check_blend_shape, after check_processor: ARG, DTYPE, SHAPE in that order).
+static int blend_processor_args(const AidProcessorArgs& a, const AidKeyframeBlend& b, AidProcessorArgs* out) {
+    if (a.ctx || a.ip || (a.mode != AID_MODE_INNER && a.mode != AID_MODE_OUTER)) return AID_ERR_ARG;
+    const int rc = check_blend_arg(&b, a.n_frames, a.n_plain);
+    if (rc != AID_OK) return rc;
+    *out = a;
+    out->coef = b.weights;
+    out->begin = out->end = 0;
+    return AID_OK;
+}
+
+size_t aid_processor_kf_blend_workspace_bytes(const AidProcessorArgs* args, const AidKeyframeBlend* b) {
+    if (!args) return 0;
+    if (!b) return aid_processor_workspace_bytes(args);
+    AidProcessorArgs a;
+    if (blend_processor_args(*args, *b, &a) != AID_OK || check_processor(a) != AID_OK || check_blend_shape(*b) != AID_OK) return 0;
+    return carve(a, a.mode == AID_MODE_OUTER ? b->n_corners : 0, b->n_corners).total;
+}
+
+int aid_processor_kf_blend_fwd(const AidProcessorArgs* args, const AidKeyframeBlend* b, void* stream) {
+    return processor_impl(args, nullptr, 0, nullptr, nullptr, stream, false, nullptr, b);
+}
+
 // ``ep`` / ``kf`` (at most one of them): which copy launch stands behind the projections — a pair store's aid_endpoint_rows, the
 // key-frame stores' aid_keyframe_rows or, with ``kf_q8``, aid_keyframe_rows_q8 on 8-bit block stores.  All replays are the same call:
 // two rows more of k / V^T, filled by that launch.
 // ``cn``: a corner-weighted call (aid_processor_corners_fwd) — step 2 is the composition among the corners, nothing else differs.
+// ``kb`` (alone): that composition among recorded key frames (aid_processor_kf_blend_fwd) — OUTER: a replay with n_corners rows behind
+// the local ones as the corners; INNER: no extra rows, the mix reads the stores.
 static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_segs, int32_t n_ip_segs, const AidEndpointStore* ep,
-                          const AidKeyframeCall* kf, void* stream, bool kf_q8, const AidCorners* cn) {
+                          const AidKeyframeCall* kf, void* stream, bool kf_q8, const AidCorners* cn, const AidKeyframeBlend* kb) {
     if (!args) return AID_ERR_ARG;
     AidProcessorArgs a_local;
     const bool replay = (ep && ep->mode == AID_EP_REPLAY) || (kf && kf->mode == AID_KF_REPLAY);
@@ -979,9 +1065,17 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         const int rcc = corners_processor_args(*args, *cn, ip_segs != nullptr || n_ip_segs != 0 || ep || kf, &a_local);
         if (rcc != AID_OK) return rcc;
     }
-    const AidProcessorArgs& a = (replay || cn) ? a_local : *args;
+    if (kb) {                                             // args->coef / begin / end are not read here either
+        const int rcb = blend_processor_args(*args, *kb, &a_local);
+        if (rcb != AID_OK) return rcb;
+    }
+    const AidProcessorArgs& a = (replay || cn || kb) ? a_local : *args;
     int rc = check_processor(a);
     if (rc != AID_OK) return rc;
+    if (kb) {
+        rc = check_blend_shape(*kb);
+        if (rc != AID_OK) return rc;
+    }
     if (ep) {
         rc = check_endpoint_store(a, *ep);
         if (rc != AID_OK) return rc;
@@ -997,7 +1091,8 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         rc = check_ip_segments(ip_segs, n_ip_segs, a.n_frames);
         if (rc != AID_OK) return rc;
     }
-    const Carve cv = carve(a, replay ? 2 : 0, cn ? cn->n_corners : 0);
+    const int kv_extra = replay ? 2 : (kb && a.mode == AID_MODE_OUTER) ? kb->n_corners : 0;
+    const Carve cv = carve(a, kv_extra, cn ? cn->n_corners : kb ? kb->n_corners : 0);
     if (!a.workspace || a.workspace_bytes < cv.total || !aligned16(a.workspace)) return AID_ERR_WORKSPACE;
     char* ws = static_cast<char*>(a.workspace);
     void* q = ws + cv.q;
@@ -1138,7 +1233,7 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
     if (rc != AID_OK) return rc;
 
     // 1b. end-point store: RECORD keeps the end-point rows of this step's k / V^T, REPLAY puts the recorded rows behind the local ones
-    const int kv_rows = replay ? nctx + 2 : nctx;
+    const int kv_rows = nctx + kv_extra;
     const int begin = replay ? nctx : a.begin, end = replay ? nctx + 1 : a.end;
     if (ep) {
         AidEndpointRows er;
@@ -1178,6 +1273,29 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         }
         if (rc != AID_OK) return rc;
     }
+    int32_t blend_rows[AID_MAX_CORNERS] = {0, 0, 0, 0, 0, 0, 0, 0};      // the corners of a blend call as rows of k / V^T (INNER: none)
+    if (kb && kv_extra) {                                     // OUTER blend: one GET of the M key frames' rows behind the local ones
+        AidKeyframeRow rows[AID_KF_MAX_ROWS];
+        for (int m = 0; m < kb->n_corners; ++m) {
+            rows[m] = kb->rows[m];
+            rows[m].row = blend_rows[m] = nctx + m;
+        }
+        AidKeyframeRowsQ8 kq;
+        memset(&kq, 0, sizeof(kq));
+        kq.k = ws + cv.k; kq.vt = ws + cv.vt; kq.rows = rows; kq.step = kb->step;
+        kq.k_fs = (int64_t)l * a.c; kq.vt_fs = (int64_t)a.c * cv.lp; kq.vt_ld = cv.lp; kq.vt_cols = l;
+        kq.n_rows = kb->n_corners; kq.n_steps = kb->n_steps; kq.direction = AID_KF_GET; kq.dtype = a.dtype;
+        if (kb->q8) {
+            rc = aid_keyframe_rows_q8(&kq, stream);
+        } else {
+            AidKeyframeRows kr;
+            memset(&kr, 0, sizeof(kr));
+            kr.k = kq.k; kr.vt = kq.vt; kr.rows = rows; kr.step = kq.step; kr.k_fs = kq.k_fs; kr.vt_fs = kq.vt_fs;
+            kr.n_rows = kq.n_rows; kr.n_steps = kq.n_steps; kr.direction = AID_KF_GET; kr.dtype = a.dtype;
+            rc = aid_keyframe_rows(&kr, stream);
+        }
+        if (rc != AID_OK) return rc;
+    }
 
     // 2. interpolated attention core (INNER: interpolated K / V^T of the interior frames first)
     AidAttnArgs at;
@@ -1187,7 +1305,7 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
         // begin / end are rows of k / vt (context rows when ctx_map is given); the interpolated rows are per FRAME
         at.k2 = ws + cv.k2; at.vt2 = ws + cv.vt2;
         const int interior = a.n_frames - a.n_plain - 2;
-        if (!cn) {                                            // (a corner call mixes its own rows, below)
+        if (!cn && !kb) {                                     // (a corner / blend call mixes its own rows, below)
             rc = lerp_kv_impl(k, vt, ws + cv.k2, ws + cv.vt2, a.coef, a.n_frames, begin, end, (int64_t)l * a.c,
                               (int64_t)a.c * cv.lp, a.dtype, stream, interior > 0 ? interior : 0);
             if (rc != AID_OK) return rc;
@@ -1207,7 +1325,18 @@ static int processor_impl(const AidProcessorArgs* args, const AidIpSegment* ip_s
     at.q_prescaled = 1;
     at.seg_executed = a.seg_executed;
     at.f32_split = a.f32_attn_split;                          // (the image branch below copies it with the rest)
-    rc = cn ? attn_corners_impl(at, *cn, reinterpret_cast<float*>(ws + cv.ctab), stream) : aid_attn_fwd(&at, stream);
+    if (kb) {
+        AidCorners bc;
+        memset(&bc, 0, sizeof(bc));
+        bc.rows = blend_rows; bc.weights = kb->weights; bc.n_corners = kb->n_corners;
+        aid::MixStoresArgs ms;
+        ms.rows = kb->rows; ms.step = kb->step; ms.weights = kb->weights; ms.k2 = ws + cv.k2; ms.vt2 = ws + cv.vt2;
+        ms.n_corners = kb->n_corners; ms.n_steps = kb->n_steps; ms.q8 = kb->q8; ms.n_mix = a.n_frames - a.n_plain;
+        ms.k_fs = at.k_fs; ms.vt_fs = at.vt_fs; ms.vt_ld = cv.lp; ms.vt_cols = l; ms.dtype = a.dtype;
+        rc = attn_corners_impl(at, bc, reinterpret_cast<float*>(ws + cv.ctab), stream, a.mode == AID_MODE_INNER ? &ms : nullptr);
+    } else {
+        rc = cn ? attn_corners_impl(at, *cn, reinterpret_cast<float*>(ws + cv.ctab), stream) : aid_attn_fwd(&at, stream);
+    }
     if (rc != AID_OK) return rc;
 
     // 2b. IP-Adapter image branch: a second (short) attention launch that accumulates into o

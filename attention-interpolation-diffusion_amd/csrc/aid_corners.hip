@@ -16,81 +16,23 @@
 //                              tab[(2 + 2p) n + i]         scale_p[i] = s = a + b                  rider:  1
 //                            with a = w[i, 2p], b = (2p + 1 < M) ? w[i, 2p + 1] : 0.  A rider's weight row is not read.
 //
-// Grid-stride, no LDS, no atomics.  This object is compiled without fast-math (csrc/Makefile): the order of the sum, the exact 1 of
+// The walk and the arithmetic of the mix are mix_walk (aid_mix.hpp), shared with the store form (aid_keyframe_blend.hip).
+// Grid-stride, no LDS, no atomics.  This object is compiled without fast-math and without contraction (csrc/Makefile): the order of the sum, the exact 1 of
 // b / (0 + b) and the error terms of the f32 path are arithmetic the compiler must not rewrite.
 #include "aid_common.hpp"
 #include "aid_kernels.hpp"
+#include "aid_mix.hpp"
 
 namespace aid {
-
-template <typename T> struct Chunk {                     // one 16-byte chunk of T and its fp32 image
-    typedef typename Vec<T>::v8 V;
-    typedef f32x8 F;
-    static constexpr int E = 8;
-    static __device__ __forceinline__ F up(const V& x) { return up8<T>(x); }
-    static __device__ __forceinline__ V down(const F& x) { return cvt8<T>(x); }
-};
-template <> struct Chunk<float> {
-    typedef f32x4 V;
-    typedef f32x4 F;
-    static constexpr int E = 4;
-    static __device__ __forceinline__ F up(const V& x) { return x; }
-    static __device__ __forceinline__ V down(const F& x) { return x; }
-};
 
 template <typename T, int M>
 __global__ __launch_bounds__(256) void aid_mix_kv_kernel(const T* __restrict__ k, const T* __restrict__ vt, T* __restrict__ k2,
                                                          T* __restrict__ vt2, const float* __restrict__ w, CornerRows rows, int n_mix,
                                                          int64_t k_fs, int64_t vt_fs) {
     typedef Chunk<T> C;
-    typedef typename C::V V;
-    typedef typename C::F F;
-    constexpr int E = C::E;
-    constexpr bool exact = sizeof(T) == 4;                  // f32 storage: carry the rounding errors (see above)
-    const int64_t nk = k_fs / E, nv = vt_fs / E;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nk + nv; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool isk = i < nk;
-        const int64_t j = (isk ? i : i - nk) * E;
-        const T* const src = isk ? k : vt;
-        T* const dst = isk ? k2 : vt2;
-        const int64_t fs = isk ? k_fs : vt_fs;
-        F x[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) x[m] = C::up(*reinterpret_cast<const V*>(src + rows.row[m] * fs + j));
-        for (int f = 0; f < n_mix; ++f) {
-            F y, err;
-#pragma unroll
-            for (int e = 0; e < E; ++e) { y[e] = 0.f; err[e] = 0.f; }
-            bool first = true;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const float wm = w[(int64_t)f * M + m];     // uniform
-                if (wm == 0.f) continue;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (!exact) {
-                        y[e] = first ? wm * x[m][e] : fmaf(wm, x[m][e], y[e]);
-                    } else {
-                        const float p = wm * x[m][e];
-                        const float pe = fmaf(wm, x[m][e], -p);             // p + pe == wm * x exactly
-                        if (first) { y[e] = p; err[e] = pe; }
-                        else {
-                            const float s = y[e] + p;
-                            const float bb = s - y[e];
-                            err[e] += ((y[e] - (s - bb)) + (p - bb)) + pe;  // two-sum: s + (...) == y + p exactly
-                            y[e] = s;
-                        }
-                    }
-                }
-                first = false;
-            }
-            if (exact) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) y[e] += err[e];
-            }
-            *reinterpret_cast<V*>(dst + (int64_t)f * fs + j) = C::down(y);
-        }
-    }
+    mix_walk<T, M>([&](int m, bool isk, int64_t j) {
+        return C::up(*reinterpret_cast<const typename C::V*>((isk ? k : vt) + rows.row[m] * (isk ? k_fs : vt_fs) + j));
+    }, k2, vt2, w, n_mix, k_fs, vt_fs);
 }
 
 __global__ __launch_bounds__(64) void aid_corner_pairs_kernel(const float* __restrict__ w, float* __restrict__ tab, int n_frames,

@@ -214,6 +214,18 @@ struct CornerRows { int32_t row[AID_MAX_CORNERS]; };          // by value in the
 hipError_t mix_kv_launch(const void* k, const void* vt, void* k2, void* vt2, const float* w, const CornerRows& rows, int n_corners,
                          int n_mix, int64_t k_fs, int64_t vt_fs, int dtype, hipStream_t stream);
 hipError_t corner_pairs_launch(const float* w, float* tab, int n_frames, int n_mix, int n_corners, hipStream_t stream);
+// the same mix with block row *step of n_corners key-frame stores as the corners (aid_keyframe_blend.hip; aid_mix_kv_stores);
+// arguments checked by the caller
+struct MixStoresArgs {
+    const AidKeyframeRow* rows;                       // HOST: n_corners entries (`row` not read)
+    const int32_t* step;                              // DEVICE
+    const float*   weights;                           // DEVICE [n_mix (+ riders), n_corners]
+    void *k2, *vt2;
+    int32_t n_corners, n_steps, q8, n_mix;
+    int64_t k_fs, vt_fs;
+    int32_t vt_ld, vt_cols, dtype;                    // vt_ld / vt_cols: q8 only
+};
+hipError_t mix_kv_stores_launch(const MixStoresArgs& a, hipStream_t stream);
 hipError_t layernorm_launch(const void* x, const void* gamma, const void* beta, void* y, int64_t rows, int c, float eps,
                             int dtype, hipStream_t stream);
 hipError_t ln_stats_launch(const void* x, float* stats, int64_t rows, int c, float eps, int dtype, hipStream_t stream);

@@ -102,11 +102,9 @@ def nested_slerp(xs, w) -> FloatTensor:
     return acc
 
 
-def corner_rows_of(weights, m: int):
-    """Checks the weight matrix of a corner-weighted run over ``m`` corners and finds the corner frames: returns (``weights`` as a
-    float32 CPU tensor [N, m], ``corner_rows``) with ``corner_rows[c]`` the first frame whose row is exactly one-hot at ``c``.  Rows must
-    be non-negative and sum to 1 within 1e-6, and every corner needs such a frame; anything else raises ``ValueError`` naming the row
-    (or the corner)."""
+def weight_rows_of(weights, m: int) -> torch.Tensor:
+    """``weights`` as a float32 CPU tensor [N, m] after the row checks of a corner-weighted run: rows non-negative, finite and summing
+    to 1 within 1e-6; anything else raises ``ValueError`` naming the row."""
     if weights is None:
         raise ValueError("pass weights [N, M]: one row of corner weights per frame (grid_weights / simplex_weights build common ones)")
     w = torch.as_tensor(weights, dtype=torch.float32).detach().cpu()
@@ -120,6 +118,15 @@ def corner_rows_of(weights, m: int):
             raise ValueError(f"weights row {i} has a negative or non-finite entry: {row.tolist()}")
         if abs(float(row.to(torch.float64).sum()) - 1.0) > 1e-6:
             raise ValueError(f"weights row {i} sums to {float(row.to(torch.float64).sum())}, not 1: {row.tolist()}")
+    return w
+
+
+def corner_rows_of(weights, m: int):
+    """Checks the weight matrix of a corner-weighted run over ``m`` corners and finds the corner frames: returns (``weights`` as a
+    float32 CPU tensor [N, m], ``corner_rows``) with ``corner_rows[c]`` the first frame whose row is exactly one-hot at ``c``.  Rows must
+    be non-negative and sum to 1 within 1e-6, and every corner needs such a frame; anything else raises ``ValueError`` naming the row
+    (or the corner)."""
+    w = weight_rows_of(weights, m)
     rows = []
     for c in range(m):
         hit = [i for i in range(w.shape[0]) if float(w[i, c]) == 1.0 and int((w[i] != 0).sum()) == 1]

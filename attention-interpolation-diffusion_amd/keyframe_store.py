@@ -14,7 +14,9 @@ and per store ONE device step index and ONE set of run settings (``SETTINGS_FIEL
 replay under anything else raises.
 
 ``pipe.record_keyframes(store, names, ...)`` records; ``pipe.interpolate_between(store, a, b)`` / ``pipe.interpolate_chain(store,
-[a, b, c])`` replay: only the interior frames go through the UNet.
+[a, b, c])`` replay: only the interior frames go through the UNet.  ``pipe.interpolate_among(store, names, weights)`` renders frames
+blended among up to eight of the recorded frames (``among`` / :class:`KeyframeBlend`): the cells of a morph grid, of
+which only those that are not a key frame go through the UNet.
 
 ``KeyframeStore(storage="q8")`` keeps the K / V^T blocks in an 8-bit block format instead of the storage dtype (DESIGN.md §3.6e,
 include/aid_hip.h): 32 int8 elements share one power-of-two exponent byte — 8.25 bits per element, 0.516x of a 16-bit store and
@@ -209,11 +211,26 @@ class KeyframeStore(StepIndex):
             raise ValueError(f"a pair needs two different key frames; got {a!r} twice")
         return KeyframePair(self, str(a), str(b))
 
+    def among(self, names: Sequence[str]) -> "KeyframeBlend":
+        """1 .. 8 distinct recorded key frames as the corners of one blending run (``pipe.interpolate_among``): the M-frame sibling of
+        ``between``.  The order of ``names`` is the order of the weight columns."""
+        if isinstance(names, str):
+            raise ValueError(f"among() takes a sequence of key-frame names; got the string {names!r}")
+        names = [str(n) for n in names]
+        if not 1 <= len(names) <= ops.MAX_CORNERS:
+            raise ValueError(f"a blend takes 1 .. {ops.MAX_CORNERS} key frames; got {len(names)}")
+        for n in names:
+            self[n]
+        if len(set(names)) != len(names):
+            raise ValueError(f"a blend needs distinct key frames; got {names}")
+        return KeyframeBlend(self, names)
+
     # -- per-layer buffers ------------------------------------------------------------------------------------------------------
     def kf_args(self, layer: str, l: int, c: int, dtype: torch.dtype, device: torch.device) -> dict:
         """The ``kf`` dictionary of ``ops.processor_kf_fwd`` for one call of ``layer`` in the run the store is in: RECORD, the frames of
         the recording as rows 0 .. K-1 of the batch (their buffers are allocated at the layer's first recorded call); REPLAY, the
-        stores of the pair's begin and end frame."""
+        stores of the pair's begin and end frame; BLEND (``among``), the stores of the M key frames in weight-column order — the ``kf``
+        of ``ops.processor_kf_blend_fwd``."""
         k_fs, vt_fs = ops.endpoint_block_sizes(l, c)
         q8 = self._storage == "q8"
         if self.mode == "record":
@@ -233,7 +250,7 @@ class KeyframeStore(StepIndex):
                 self._check_block(layer, hit, k_fs, vt_fs, dtype, device, self._storage)
                 entries.append((hit[0], hit[1], row))
             return self._kf(entries, "record")
-        if self.mode == "replay":
+        if self.mode in ("replay", "blend"):
             entries = []
             for name in self._pair:
                 hit = self.frames[name].layers.get(layer)
@@ -241,8 +258,9 @@ class KeyframeStore(StepIndex):
                     raise RuntimeError(f"key frame {name!r} holds no rows of layer {layer!r}: it was recorded on another UNet")
                 self._check_block(layer, hit, k_fs, vt_fs, dtype, device, self._storage)
                 entries.append((hit[0], hit[1], 0))
-            return self._kf(entries, "replay")
-        raise RuntimeError("the key-frame store is attached to a processor outside a run (record_keyframes / interpolate_between)")
+            return self._kf(entries, self.mode)
+        raise RuntimeError("the key-frame store is attached to a processor outside a run (record_keyframes / interpolate_between / "
+                           "interpolate_among)")
 
     def _kf(self, entries, mode: str) -> dict:
         """(a native store's dictionary is what it always was; a q8 store's names its storage)"""
@@ -271,9 +289,14 @@ class KeyframePair:
     reads of an ``EndpointStore`` (``recorded``, ``begin_replay``, ``set_step``, ``latents``, ``abort``), answered from the two frames."""
 
     recorded = True
+    _mode = "replay"             # what the store's ``mode`` is during the run; a subclass (KeyframeBlend) sets its own and ``_names``
 
     def __init__(self, store: KeyframeStore, a: str, b: str):
         self.store, self.a, self.b = store, a, b
+
+    def _names(self) -> Tuple[str, ...]:
+        """The key frames of the run, as ``store._pair`` holds them during it."""
+        return (self.a, self.b)
 
     @property
     def mode(self) -> Optional[str]:
@@ -297,7 +320,7 @@ class KeyframePair:
             raise RuntimeError("the store is in use by another run")
         t = int(signature["num_inference_steps"])
         st.check(signature, int(t * float(signature["warmup_ratio"])) if signature.get("late") == "self" else t)
-        st.mode, st._pair = "replay", (self.a, self.b)
+        st.mode, st._pair = self._mode, self._names()
         st._ensure_step(device)
 
     def set_step(self, i: int) -> None:
@@ -308,3 +331,22 @@ class KeyframePair:
 
     def kf_args(self, layer: str, l: int, c: int, dtype: torch.dtype, device: torch.device) -> dict:
         return self.store.kf_args(layer, l, c, dtype, device)
+
+
+class KeyframeBlend(KeyframePair):
+    """M <= 8 key frames of a :class:`KeyframeStore` as the corners of ONE blending run (``KeyframeStore.among``): ``begin_replay``
+    (the same settings and AID-step check), ``set_step`` and ``abort`` are the pair's; ``latents`` are the M final latents and
+    ``kf_args`` names the M stores of a layer (``mode="blend"``)."""
+
+    _mode = "blend"
+
+    def __init__(self, store: KeyframeStore, names: Sequence[str]):
+        self.store, self.names = store, tuple(names)
+
+    def _names(self) -> Tuple[str, ...]:
+        return self.names
+
+    @property
+    def latents(self) -> torch.Tensor:
+        """[M, ...]: the final latents of the key frames, in weight-column order."""
+        return torch.cat([self.store[n].final for n in self.names], dim=0)

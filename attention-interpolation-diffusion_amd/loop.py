@@ -22,7 +22,7 @@ from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 
-from .processors import (CornerInterpolatedAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
+from .processors import (CornerInterpolatedAttnProcessor, KeyframeBlendAttnProcessor, HipAttnProcessor, HipIPAdapterAttnProcessor, InnerInterpolatedAttnProcessor,
                          InnerInterpolatedIPAttnProcessor, InterpolatedAttnProcessor, OuterInterpolatedAttnProcessor,
                          OuterInterpolatedIPAttnProcessor, ScaleControlIPAttnProcessor, cache_generation, clear_weight_caches)
 
@@ -114,6 +114,27 @@ def install_corner_processors(unet, weights, corner_rows: Sequence[int], early: 
     for name in current:
         procs[name] = CornerInterpolatedAttnProcessor(w.clone(), corner_rows, mode=early.split("_")[1],
                                                       is_fused=early.startswith("fused"), original_attn=HipAttnProcessor())
+    unet.set_attn_processor(procs)
+
+
+def install_blend_processors(unet, weights, blend, early: str = "fused_outer", corner_ctx: Optional[torch.Tensor] = None) -> None:
+    """One ``KeyframeBlendAttnProcessor`` per attention layer: local frame i blends the recorded key frames of ``blend``
+    (``KeyframeStore.among(names)``) with the weight row ``weights[i]`` (``[N_local, M]``), in the mode ``early`` names.  Each processor
+    learns its layer's name in the store (its key in ``attn_processors``) and gets its own copy of the weights; ``corner_ctx``
+    [M, L, Cc] — the key frames' cond contexts — serves the cross-attention layers.  IP-Adapter layers are refused, as for
+    ``install_corner_processors``."""
+    if early not in EARLY_MODES:
+        raise ValueError(f"early must be one of {EARLY_MODES}")
+    current = dict(unet.attn_processors)
+    if any(_adapter_of(cur) is not None for cur in current.values()):
+        raise NotImplementedError("a key-frame blend on a UNet with IP-Adapter layers: the image branches interpolate between two "
+                                  "end points only")
+    clear_weight_caches()
+    w = torch.as_tensor(weights, dtype=torch.float32).detach().cpu()
+    procs = {}
+    for name in current:
+        procs[name] = KeyframeBlendAttnProcessor(w.clone(), blend, mode=early.split("_")[1], is_fused=early.startswith("fused"),
+                                                 original_attn=HipAttnProcessor(), layer=name, corner_ctx=corner_ctx)
     unet.set_attn_processor(procs)
 
 

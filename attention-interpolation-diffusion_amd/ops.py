@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import (DTYPE_BF16, DTYPE_F16, DTYPE_F32, EP_GET, EP_PUT, EP_RECORD, EP_REPLAY, IP_MAX_SEGMENTS, IP_NONE, IP_PLAIN, IP_SAME,
                    KF_GET, KF_MAX_ROWS, KF_PUT, KF_RECORD, KF_REPLAY, MAX_CORNERS, MODE_INNER, MODE_OUTER, MODE_PLAIN,
-                   AidAttnArgs, AidCorners, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeCall,
+                   AidAttnArgs, AidCorners, AidEndpointRows, AidEndpointStore, AidGemmProblem, AidIpAttnArgs, AidIpSegment, AidKeyframeBlend, AidKeyframeCall,
                    AidKeyframeRow, AidKeyframeRows, AidKeyframeRowsQ8, AidProcessorArgs)
 
 MODES = {"plain": MODE_PLAIN, "inner": MODE_INNER, "outer": MODE_OUTER}
@@ -722,7 +722,8 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
     one launch after the text attention — several IP-Adapters per layer, regional masks as ``row_weight``.  A cross-attention
     ``mode="plain"`` call without ``ip``, float16 / bfloat16; ``attn_bias`` is allowed and covers the text scores only.
     ``ep``: the end-point store of the layer, see ``processor_ep_fwd``.  ``kf``: key-frame stores of the layer, see
-    ``processor_kf_fwd`` (one of the two at most).  ``corners``: a corner-weighted call, see ``processor_corners_fwd`` (no store, no
+    ``processor_kf_fwd`` (one of the two at most; ``kf["mode"] == "blend"``: the corners of a corner-weighted call are recorded key
+    frames, see ``processor_kf_blend_fwd``).  ``corners``: a corner-weighted call, see ``processor_corners_fwd`` (no store, no
     image branch; ``coef`` / ``begin`` / ``end`` are not read)."""
     lib = _lib.load()
     split = f32_split_code(f32_precision)
@@ -852,6 +853,14 @@ def processor_fwd(x: torch.Tensor, ctx: Optional[torch.Tensor], wq: torch.Tensor
             raise ValueError("an end-point store belongs to a self-attention call: no ip_segments")
         est = _endpoint_store_args(ep, s, c, x.dtype)
         nbytes = lib.aid_processor_ep_workspace_bytes(C.byref(a), C.byref(est))
+    elif kf is not None and kf.get("mode") == "blend":               # the corners of the call are recorded key frames
+        if seg_arr is not None or ip is not None or ctx is not None:
+            raise ValueError("key-frame stores belong to a self-attention call: no context, no image branch")
+        if mode == "plain":
+            raise ValueError("a key-frame blend is an interpolated (inner / outer) call")
+        kcall, _kf_rows = _keyframe_blend_args(kf, n, s, c, x.dtype)
+        kf_size, kf_fwd, kf_name = lib.aid_processor_kf_blend_workspace_bytes, lib.aid_processor_kf_blend_fwd, "aid_processor_kf_blend_fwd"
+        nbytes = kf_size(C.byref(a), C.byref(kcall))
     elif kf is not None:
         if seg_arr is not None:
             raise ValueError("key-frame stores belong to a self-attention call: no ip_segments")
@@ -1095,6 +1104,79 @@ def processor_kf_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
     if kf.get("mode") == "replay" and plain:
         raise ValueError("key-frame stores replay into an interpolated (inner / outer) call")
     return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, kf=kf, **kwargs)
+
+
+# ---- key-frame blend (aid_hip.h: aid_mix_kv_stores, aid_processor_kf_blend_fwd) -----------------------------------------------------
+def _keyframe_blend_args(kf: dict, n_frames: int, l: int, c: int, dtype: torch.dtype):
+    """AidKeyframeBlend of ``kf`` = dict(entries=[(k_store, vt_store, _), ...], step=int32 device [1], weights=float32 device
+    [n_frames, M][, storage="native" | "q8"]) for a call with blocks of [l, c] keys; returns (struct, the host array it points at)."""
+    k_fs, vt_fs = endpoint_block_sizes(l, c)
+    entries = [(k_, v_, 0) for k_, v_, _ in kf["entries"]]
+    if not 1 <= len(entries) <= MAX_CORNERS:
+        raise ValueError(f"a call blends 1 .. {MAX_CORNERS} key frames; got {len(entries)}")
+    storage = _check_storage(kf.get("storage", "native"))
+    arr, n_steps = _keyframe_row_array(entries, kf["step"], k_fs, vt_fs, dtype, storage)
+    w = kf.get("weights")
+    _require_gpu(w)
+    if w is None or w.dtype != torch.float32 or tuple(w.shape) != (n_frames, len(arr)) or not w.is_contiguous():
+        raise ValueError(f"weights must be a contiguous float32 device tensor [{n_frames}, {len(arr)}] (one row per local frame, one "
+                         f"column per key frame); got {None if w is None else (tuple(w.shape), w.dtype)}")
+    b = AidKeyframeBlend()
+    b.rows, b.step, b.weights, b.n_corners, b.n_steps, b.q8 = arr, kf["step"].data_ptr(), w.data_ptr(), len(arr), n_steps, int(storage == "q8")
+    return b, arr
+
+
+def mix_kv_stores(entries, step: torch.Tensor, weights: torch.Tensor, shape_k: Sequence[int], shape_vt: Sequence[int], dtype: torch.dtype,
+                  n_plain: int = 0, storage: str = "native", vt_cols: Optional[int] = None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``k2[i] = sum_m weights[i, m] K_m[step]`` (and V^T -> vt2) for the first ``N - n_plain`` frames, read straight from slot
+    ``step[0]`` of M <= 8 key-frame stores in one streaming launch (``aid_mix_kv_stores``) — ``keyframe_rows[_q8]`` "get" followed by
+    ``mix_kv``, bit for bit, without the M rows in between.  ``entries`` = [(k_store, vt_store, _), ...] as ``keyframe_rows`` /
+    ``keyframe_rows_q8`` (``storage="q8"``) take them, ``shape_k`` = (L, C) and ``shape_vt`` = (C, Lp) the call's blocks, ``dtype`` its
+    element type, ``weights`` float32 device [N, M]; q8: of every vt row the first ``vt_cols`` columns (default: all) are stored, the
+    others are +0.  Returns (k2 [N, L, C], vt2 [N, C, Lp]) — ``out`` or fresh tensors; the rows of the last ``n_plain`` frames are not
+    written.  A step outside the stores writes nothing."""
+    (l, c), (c2, lp) = (int(v) for v in shape_k), (int(v) for v in shape_vt)
+    if weights.ndim != 2:
+        raise ValueError("weights must be [N, M]")
+    dev = _require_gpu(weights, step, *(out or ()))
+    n = weights.shape[0]
+    entries = list(entries)
+    storage = _check_storage(storage)
+    if not 1 <= len(entries) <= MAX_CORNERS:
+        raise ValueError(f"a call blends 1 .. {MAX_CORNERS} key frames; got {len(entries)}")
+    arr, n_steps = _keyframe_row_array([(k_, v_, 0) for k_, v_, _ in entries], step, l * c, c2 * lp, dtype, storage)
+    if weights.dtype != torch.float32 or weights.shape[1] != len(arr) or not weights.is_contiguous():
+        raise ValueError(f"weights must be a contiguous float32 device tensor [N, {len(arr)}]")
+    if out is None:
+        out = (torch.empty(n, l, c, dtype=dtype, device=dev), torch.empty(n, c2, lp, dtype=dtype, device=dev))
+    k2, vt2 = out
+    if k2.dtype != dtype or vt2.dtype != dtype or tuple(k2.shape) != (n, l, c) or tuple(vt2.shape) != (n, c2, lp) \
+            or not k2.is_contiguous() or not vt2.is_contiguous():
+        raise ValueError("out must be (k2 [N, L, C], vt2 [N, C, Lp]) contiguous")
+    b = AidKeyframeBlend()
+    b.rows, b.step, b.weights, b.n_corners, b.n_steps, b.q8 = arr, step.data_ptr(), weights.data_ptr(), len(arr), n_steps, int(storage == "q8")
+    with _on(dev):
+        _lib.check(_lib.load().aid_mix_kv_stores(C.byref(b), k2.data_ptr(), vt2.data_ptr(), n, int(n_plain), l * c, c2 * lp, lp,
+                                                 lp if vt_cols is None else int(vt_cols), _dtype_code(k2), _stream()), "aid_mix_kv_stores")
+    return k2, vt2
+
+
+def processor_kf_blend_fwd(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, wo: torch.Tensor,
+                           bo: Optional[torch.Tensor], heads: int, *, kf: dict, weights: torch.Tensor, **kwargs) -> torch.Tensor:
+    """A SELF-attention corner-weighted call whose corners are recorded key frames (``aid_processor_kf_blend_fwd``) — still one
+    library call.  ``x`` holds the LOCAL frames only (the AID frames, then ``n_plain`` riders); ``kf`` = dict(entries=[(k_store,
+    vt_store, _) x M], step=int32 device [1], mode="blend"[, storage="q8"]) names the M <= 8 key frames' stores of the layer,
+    ``weights`` float32 device [N, M] the frames' weight rows (as ``processor_corners_fwd``).  mode="outer": one "get" puts the M
+    recorded rows behind the local ones and the corner composition runs on them; mode="inner": ``mix_kv_stores`` writes the mixed
+    rows straight from the stores.  Every other keyword is ``processor_fwd``'s except ``coef`` / ``begin`` / ``end`` (not read) and
+    the contexts, image branches and other stores, which the call does not take."""
+    if kf is None or kf.get("mode") != "blend":
+        raise ValueError("processor_kf_blend_fwd needs the layer's key-frame stores as kf=dict(..., mode='blend')")
+    for name in ("coef", "begin", "end", "ip", "ip_segments", "ep", "corners", "kv_cached", "ctx_map"):
+        if kwargs.get(name) is not None:
+            raise ValueError(f"a key-frame blend takes no {name}=")
+    return processor_fwd(x, None, wq, wk, wv, wo, bo, heads, kf=dict(kf, weights=weights), **kwargs)
 
 
 # ---- corner-weighted AID (aid_hip.h: aid_mix_kv, aid_attn_corners_fwd, aid_processor_corners_fwd) ------------------------------------

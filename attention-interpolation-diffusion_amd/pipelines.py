@@ -46,11 +46,11 @@ from . import ops
 from . import processors as P
 from ._lib import KF_MAX_ROWS
 from .attn_shim import AttnStackUNet
-from .interp import (corner_rows_of, generate_beta_tensor, linear_interpolation, nested_slerp, slerp,
+from .interp import (corner_rows_of, weight_rows_of, generate_beta_tensor, linear_interpolation, nested_slerp, slerp,
                      spherical_interpolation)
 from .endpoint_store import EndpointStore, run_settings, run_signature
 from .keyframe_store import KeyframePair, KeyframeStore
-from .loop import EARLY_MODES, install_corner_processors, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store, set_keyframe_store
+from .loop import EARLY_MODES, install_blend_processors, install_corner_processors, install_sequence_processors, set_aid_active, set_ctx_index, set_endpoint_store, set_keyframe_store
 from .sequence import SequenceBatch, prepare_sequence, prepare_single
 
 
@@ -1038,6 +1038,128 @@ class InterpolationStableDiffusionPipeline:
         parts = [self.interpolate_between(store, names[i], names[i + 1], size=size, **kwargs) for i in range(len(names) - 1)]
         parts = parts[:1] + [p_[1:] for p_ in parts[1:]]
         return torch.cat(parts) if torch.is_tensor(parts[0]) else np.concatenate(parts)
+
+    # -- key frames: render frames blended among up to eight of them -------------------
+    @torch.no_grad()
+    def interpolate_among(self, store: KeyframeStore, names: Sequence[str], weights, guide_prompt: Optional[str] = None,
+                          embeds_guide=None, negative_prompt: str = "", early: str = "fused_outer", late: str = "self",
+                          warmup_ratio: float = 0.5, frame_latents: Optional[torch.Tensor] = None, max_frames: Optional[int] = None,
+                          num_inference_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
+                          guidance_rescale: float = 0.0, use_graphs: Optional[bool] = None,
+                          cross_attention_kwargs: Optional[Dict[str, Any]] = None, output_type: str = "np", **image_inputs):
+        """Render N frames blended among the M <= 8 recorded key frames ``names`` of ``store`` — ``interpolate_corners`` whose corners
+        are recorded: only the frames that are not a key frame go through the UNet, their AID steps attend to the key frames' recorded
+        keys / values.  ``weights`` [N, M] (columns in the order of ``names``): rows non-negative, summing to 1 within 1e-6, anything
+        else raises ``ValueError`` naming the row (``grid_weights`` / ``simplex_weights`` give such rows).  A frame whose row is exactly
+        one-hot IS that key frame: its output is the stored final latent and it is not rendered.  Every other frame starts from the
+        ``nested_slerp`` of the key frames' stored initial latents (or its row of ``frame_latents`` [N, C, h, w]) with the weight-mixed
+        key-frame embeddings, exactly as ``interpolate_corners`` mixes them; with a guide prompt every rendered frame shares the
+        guide's context.  One UNet call ``[cond n ; uncond n]`` per step over the rendered frames only, the second half as plain
+        riders; ``max_frames`` renders them in runs of at most that many, joined in weight-row order.  ``num_inference_steps`` /
+        ``guidance_scale`` default to the store's; settings that differ from the recording's, or a run that needs more AID steps than
+        were recorded, raise ``ValueError`` as ``interpolate_between`` does.  IP-Adapter image inputs raise ``NotImplementedError``."""
+        for name in image_inputs:
+            if name in ("image_start", "image_end", "image_embeds_start", "image_embeds_end", "images", "image_embeds",
+                        "ip_adapter_image", "ip_adapter_image_embeds"):
+                raise NotImplementedError(f"interpolate_among takes no image inputs ({name}): the IP-Adapter image branches "
+                                          "interpolate between two end points only")
+            raise TypeError(f"interpolate_among() got an unexpected keyword argument {name!r}")
+        if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
+            raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
+        blend = store.among(names)
+        m = len(blend.names)
+        w = weight_rows_of(weights, m)
+        n_all = w.shape[0]
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError(f"max_frames must be None or >= 1; got {max_frames}")
+        frames = [store[n_] for n_ in blend.names]
+        onehot = [int(torch.nonzero(w[i] == 1.0)[0]) if bool((w[i] == 1.0).any()) and int((w[i] != 0).sum()) == 1 else None
+                  for i in range(n_all)]
+        render = [i for i in range(n_all) if onehot[i] is None]
+        if frame_latents is not None and tuple(frame_latents.shape) != (n_all,) + tuple(frames[0].latent.shape[1:]):
+            raise ValueError(f"frame_latents must be [{n_all}, ...] like the key frames' latents; got {tuple(frame_latents.shape)}")
+        steps = store.settings["num_inference_steps"] if num_inference_steps is None else num_inference_steps
+        if guidance_scale is None:
+            gs = store.settings["guidance_scale"]
+            gs = gs[0] if isinstance(gs, tuple) else gs
+        else:
+            gs = guidance_scale
+        gr = _check_rescale(guidance_rescale)
+        self._guidance_scale, self._guidance_rescale = gs, gr
+        dev, dtype = self._unet_device_dtype()
+        cak = cross_attention_kwargs
+        ls = cak.get("scale", None) if cak is not None else None
+        sides = [self._split(self._embed(None, negative_prompt, f_.embeds, ls)) for f_ in frames]
+        guide = None
+        if guide_prompt is not None or embeds_guide is not None:
+            guide = self._split(self._embed(guide_prompt, negative_prompt, embeds_guide, ls))
+        self.scheduler.set_timesteps(steps, device=dev)
+        warmup_steps = int(steps * warmup_ratio)
+        sig = dict(run_settings(num_inference_steps=steps, guidance_scale=gs, dtype=dtype, timesteps=self.scheduler.timesteps,
+                                unet=self.unet, lora_scale=ls, guidance_rescale=gr), warmup_ratio=float(warmup_ratio), late=late)
+        corner_ctx = torch.cat([s_[0][0] for s_ in sides]).to(dev, dtype).contiguous()
+        cl = [f_.latent.to(dev, dtype) for f_ in frames]
+
+        def mixed(rows, slot: int, side: int):
+            """[n, ...]: key-frame tensors ``sides[.][side][slot]`` mixed with the weight rows ``rows`` (none of them one-hot)."""
+            src = [sides[c][side][slot] for c in range(m)]
+            acc = torch.float64 if src[0].dtype == torch.float64 else torch.float32
+            stack = torch.cat([t_.to(acc) for t_ in src], dim=0)
+            return torch.cat([torch.tensordot(w[i].to(stack.device, acc), stack, dims=1).unsqueeze(0).to(src[0].dtype) for i in rows])
+
+        out = [None] * n_all
+        finals = blend.latents
+        for i in range(n_all):
+            if onehot[i] is not None:
+                out[i] = finals[onehot[i]:onehot[i] + 1].to(dev, dtype)
+        group = len(render) if max_frames is None else int(max_frames)
+        installed = dict(self.unet.attn_processors)          # restored at the end, as interpolate does
+        for g0 in range(0, len(render), max(group, 1)):
+            rows = render[g0:g0 + group]
+            n = len(rows)
+            if guide is not None:     # one context row per frame, as interpolate hands them over; ctx_index names the ONE distinct row
+                cond, unc = guide[0][0].expand(n, -1, -1), guide[1][0].expand(n, -1, -1)
+                idx = [0] * n
+                pooled = (guide[0][1].expand(n, -1), guide[1][1].expand(n, -1)) if len(sides[0][0]) > 1 else None
+            else:
+                cond, unc, idx = mixed(rows, 0, 0), mixed(rows, 0, 1), None
+                pooled = (mixed(rows, 1, 0), mixed(rows, 1, 1)) if len(sides[0][0]) > 1 else None
+            cond, unc = cond.to(dev, dtype).contiguous(), unc.to(dev, dtype).contiguous()
+            lat = frame_latents[rows].to(dev, dtype) if frame_latents is not None else \
+                torch.cat([nested_slerp(cl, w[i]) for i in rows], dim=0)
+            blend.begin_replay(sig, dev)
+            try:
+                procs = {}
+                for mode in {early} | ({late} - {"self"}):
+                    install_blend_processors(self.unet, w[rows], blend, early=mode, corner_ctx=corner_ctx)
+                    procs[mode] = dict(self.unet.attn_processors)
+                graphs = _PassGraphs(_use_graphs(use_graphs, dev))
+                ctx_both = torch.cat([cond, unc])           # ONE tensor for the whole run: the text K / V cache keys on it
+                added_both = self._added_cond(None if pooled is None else torch.cat(pooled), 2 * n)
+                idx_both = None if idx is None else idx + [j + 1 for j in idx]
+
+                def both_pass(x, t):
+                    return self._unet(torch.cat([x, x]), t, ctx_both, added_both, cak)
+
+                for i, t in enumerate(self.scheduler.timesteps):
+                    x = self.scheduler.scale_model_input(lat, t)
+                    td = _dev_scalar(t, dev) if graphs.enabled else t
+                    mode = early if i < warmup_steps else late
+                    self.unet.set_attn_processor(procs[mode] if mode != "self" else procs[early])
+                    if mode != "self":
+                        blend.set_step(i)
+                    set_aid_active(self.unet, mode != "self", plain_tail=n if mode != "self" else 0)
+                    set_ctx_index(self.unet, idx_both)
+                    both = graphs.run(("both", mode), both_pass, x=x, t=td)
+                    noise = _guided_noise(both[:n], both[n:], gs, gr)
+                    lat = self.scheduler.step(noise, t, lat, return_dict=False)[0]
+                for j, i in enumerate(rows):
+                    out[i] = lat[j:j + 1]
+            finally:
+                blend.abort()
+                set_ctx_index(self.unet, None)
+                self.unet.set_attn_processor(installed)
+        return self._decode(torch.cat(out, dim=0), output_type)
 
     # -- small shape helpers (overridden by the XL class) ----------------------------------------------
     def _installed_aid_mode(self):

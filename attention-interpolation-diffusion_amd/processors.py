@@ -704,7 +704,11 @@ class CornerInterpolatedAttnProcessor(InterpolatedAttnProcessor):
         kw = dict(ln=_ln_of(norm), add_to=hidden_states, ln_folded=_ln_folded(attn, norm, encoder_hidden_states is not None))
         if not self.activated:
             return _run_text(self, attn, hidden_states, encoder_hidden_states, None, None, "plain", ctx_index, **kw)
-        return _run_corners(self, attn, hidden_states, encoder_hidden_states, None, None, ctx_index, **kw)
+        return self._run(attn, hidden_states, encoder_hidden_states, None, None, ctx_index, **kw)
+
+    def _run(self, *args, **kw):
+        """The activated call (KeyframeBlendAttnProcessor runs it against recorded key frames instead)."""
+        return _run_corners(self, *args, **kw)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, ctx_index=None):
         ctx_index = self.ctx_index if ctx_index is None else ctx_index
@@ -714,7 +718,96 @@ class CornerInterpolatedAttnProcessor(InterpolatedAttnProcessor):
                     return self.original_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index=ctx_index)
                 return self.original_attn(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
             return _run_text(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, "plain", ctx_index)
-        return _run_corners(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index)
+        return self._run(attn, hidden_states, encoder_hidden_states, attention_mask, temb, ctx_index)
+
+
+class KeyframeBlendAttnProcessor(CornerInterpolatedAttnProcessor):
+    r"""Build-specific: the corner-weighted processor whose corners are RECORDED key frames.  The batch holds the
+    local frames only — no corner rows: ``weights`` is ``[N_local, M]`` over the M key frames of ``blend``
+    (``KeyframeStore.among(names)``, in its order), with the semantics of the parent's attribute (the device copy is rewritten in
+    place; a change inside a capture raises).  Self-attention is one ``ops.processor_kf_blend_fwd`` call on the layer's stores
+    (``endpoint_layer`` names the layer); cross-attention needs no store: ``corner_ctx`` ([M, L, Cc], the key frames' cond contexts) is
+    appended behind the (shared) local contexts and the call is ``ops.processor_corners_fwd``.  De-activated it is the plain path."""
+    _mode = "blend"
+
+    def __init__(self, weights, blend, mode: str = "outer", is_fused: bool = True, original_attn=None, layer: Optional[str] = None,
+                 corner_ctx: Optional[torch.Tensor] = None):
+        w = weights if torch.is_tensor(weights) else torch.as_tensor(weights, dtype=torch.float32)
+        m = w.shape[1] if w.ndim == 2 else 0
+        names = getattr(blend, "names", None)
+        if names is not None and len(names) != m:
+            raise ValueError(f"weights has {m} columns; the blend holds {len(names)} key frames")
+        super().__init__(w, [0] * m, mode=mode, is_fused=is_fused, original_attn=original_attn)     # (no corner is a row of the batch)
+        self.blend = blend
+        self.endpoint_layer = layer
+        self.corner_ctx = corner_ctx
+
+    def _run(self, *args, **kw):
+        return _run_blend(self, *args, **kw)
+
+
+def _run_blend(proc: KeyframeBlendAttnProcessor, attn, hidden_states, encoder_hidden_states, attention_mask, temb,
+               ctx_index=None, ln=None, add_to=None, ln_folded=None):
+    """``_run_corners`` with recorded key frames as the corners: self-attention reads the layer's stores
+    (``ops.processor_kf_blend_fwd``), cross-attention appends the key frames' contexts (``ops.processor_corners_fwd``)."""
+    if isinstance(encoder_hidden_states, tuple):
+        raise NotImplementedError("KeyframeBlendAttnProcessor on an IP-Adapter layer ((text, [image_embeds]) contexts): the image "
+                                  "branches interpolate between two end points only")
+    for name, what in (("endpoint_store", "an end-point store"), ("keyframe_store", "a two-frame key-frame replay"),
+                       ("endpoint_exchange", "endpoint_exchange")):
+        if getattr(proc, name, None) is not None:
+            raise NotImplementedError(f"{what} with a key-frame blend: the blend names its key frames itself (KeyframeStore.among)")
+    residual, x, ctx, shape4, mask = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+    wq, wk, wv, wo, bo = _weights(attn)
+    bias = _score_bias(mask, x, x.shape[1] if ctx is None else ctx.shape[1], proc.is_fused, type(proc).__name__)
+    w_dev = proc._weights_device(x.device, x.shape[0])
+    n, m = x.shape[0], proc.weights.shape[1]
+    kw = dict(mode=proc.mode, fused=proc.is_fused, n_plain=proc.plain_tail, ln=ln, residual=add_to, ln_folded=ln_folded, attn_bias=bias)
+    if ctx is None:
+        if not x.is_cuda:
+            raise NotImplementedError("a key-frame blend on a CPU tensor: the stores live in device memory and are read by the HIP "
+                                      "kernels (there is no CPU path)")
+        layer = proc.endpoint_layer or f"layer@{id(attn):x}"
+        y = ops.processor_kf_blend_fwd(x, wq, wk, wv, wo, bo, attn.heads, weights=w_dev,
+                                       kf=proc.blend.kf_args(layer, x.shape[1], x.shape[2], x.dtype, x.device),
+                                       lora=lora.args(attn, x.dtype, x.device, False), **kw)
+        return _epilogue(attn, y, residual, shape4)
+    cctx = proc.corner_ctx
+    if cctx is None or cctx.ndim != 3 or cctx.shape[0] != m or tuple(cctx.shape[1:]) != tuple(ctx.shape[1:]):
+        raise RuntimeError(f"a key-frame blend's cross-attention needs `corner_ctx` [{m}, L, Cc]: the cond contexts of the key frames "
+                           f"(got {None if cctx is None else tuple(cctx.shape)} next to contexts {tuple(ctx.shape)})")
+    ctx_index = proc.ctx_index if ctx_index is None else ctx_index
+    base = [int(i) for i in ctx_index] if ctx_index is not None else list(range(n))
+    nctx = max(base) + 1
+    if len(base) != n or min(base) < 0 or sorted(set(base)) != list(range(nctx)):
+        raise RuntimeError("ctx_index must have one entry per local frame and use every context row 0 .. n_distinct-1")
+    # [distinct local contexts ; the M key frames' contexts] is loop-invariant: built once per (caller's context tensor, map), as the
+    # replay of two end points builds its own (_run_text) — it is the tensor the text K / V cache keys on
+    ck = ("blend", tuple(base), ctx.data_ptr(), _version_of(ctx), tuple(ctx.shape), ctx.dtype, ctx.device,
+          cctx.data_ptr(), _version_of(cctx), tuple(cctx.shape), cctx.dtype, cctx.device)
+    hit = proc._ctx_cache.get(ck)
+    if hit is not None and (hit[1]() is not ctx or hit[2]() is not cctx):
+        proc._ctx_cache.pop(ck, None)
+        hit = None
+    if hit is None:
+        own = ctx
+        if own.shape[0] == n and nctx != n:
+            own = own.index_select(0, torch.tensor([base.index(r) for r in range(nctx)], device=ctx.device))
+        elif own.shape[0] != nctx:
+            raise RuntimeError(f"encoder_hidden_states has {ctx.shape[0]} rows; the frame -> context map needs {nctx}")
+        for old_key in [k_ for k_ in proc._ctx_cache if k_ and k_[0] == "blend"]:
+            proc._ctx_cache.pop(old_key, None)                    # one live entry per processor (per run)
+
+        def _drop(_ref, cache=proc._ctx_cache, key=ck):
+            cache.pop(key, None)
+        hit = (torch.cat([own, cctx.to(ctx.dtype)], dim=0).contiguous(), weakref.ref(ctx, _drop), weakref.ref(cctx, _drop))
+        proc._ctx_cache[ck] = hit
+    full = hit[0]
+    ctx2, ctx_map, idx2 = _shared_context(proc._ctx_cache, base + [nctx + i for i in range(m)], full, n + m)
+    kv = _text_kv(attn, full, ctx2, idx2, wk, wv)
+    y = ops.processor_corners_fwd(x, ctx2, wq, wk, wv, wo, bo, attn.heads, weights=w_dev, rows=[idx2[n + i] for i in range(m)],
+                                  ctx_map=ctx_map[:n], kv_cached=kv, lora=lora.args(attn, x.dtype, x.device, True, kv=kv is None), **kw)
+    return _epilogue(attn, y, residual, shape4)
 
 
 def _check_corner_weights(weights, corner_rows) -> torch.Tensor:

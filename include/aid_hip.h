@@ -734,6 +734,57 @@ size_t aid_processor_corners_workspace_bytes(const AidProcessorArgs* args /* hos
 int    aid_processor_corners_fwd(const AidProcessorArgs* args /* host */, const AidCorners* corners /* host */, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Key-frame blend: a corner-weighted call whose corners are RECORDED key frames — the store form of the section above (no ABI version
+ * change: three new entry points and one struct; no existing struct, constant or entry point changes).  Corner m is block row *step
+ * of key frame m's store (AidKeyframeRow.k_store / vt_store, `row` ignored; the same store may stand twice), 1 <= M <= AID_MAX_CORNERS
+ * = AID_KF_MAX_ROWS.  Native stores ([n_steps, k_fs] / [n_steps, vt_fs] elements of the call dtype, q8 == 0) or 8-bit block stores
+ * ([n_steps, aid_q8_block_bytes(.)] bytes, q8 == 1) as aid_keyframe_rows / aid_keyframe_rows_q8 PUT leaves them.  `weights` is
+ * AidCorners.weights: DEVICE fp32 [n_frames, M], read by the kernels, the riders' rows not read.
+ *
+ * aid_mix_kv_stores — the INNER mix read straight from the stores, one streaming launch:
+ *   k2[i] = sum_m w[i, m] * K_m[*step]    vt2[i] = sum_m w[i, m] * V^T_m[*step]       for i in [0, n_frames - n_plain)
+ * It is aid_keyframe_rows[_q8] GET of the M rows followed by aid_mix_kv on them, bit for bit, without the M rows in between: the
+ * arithmetic is aid_mix_kv's (fp32 products and sum in corner order, one rounding; a weight of exactly 0 is skipped, so a one-hot row
+ * returns the corner's bits — for q8 the dequantised ones — and a skipped corner's block may hold anything; f32 storage carries the
+ * rounding errors along).  A q8 value is q * 2^e as GET rounds it to the call dtype; V^T pad columns (column >= vt_cols of a row of
+ * vt_ld) of q8 stores enter as +0, so they are +0 in every mixed row.
+ * Reads exactly block row *step of every store — [*step * k_fs .. + k_fs) elements (native) or bytes [0, n + ceil(n / 32)) of the
+ * block row (q8), each ONCE per launch — the one int32 *step, and w[i, 0 .. M) for i < n_frames - n_plain.  Writes exactly
+ * k2[i * k_fs .. + k_fs) and vt2[i * vt_fs .. + vt_fs) for i < n_frames - n_plain: whole blocks, gap rows and pad columns included; the
+ * riders' rows are untouched.  A *step outside [0, n_steps) writes nothing.  n_plain == n_frames launches nothing.
+ * AID_ERR_ARG: b, rows, a store, step, weights, k2 or vt2 NULL, n_corners outside 1 .. AID_MAX_CORNERS, n_steps < 1, q8 outside
+ * {0, 1}, n_frames < 1, n_plain outside [0, n_frames], step not 4-byte aligned; AID_ERR_DTYPE; AID_ERR_SHAPE: k_fs / vt_fs not
+ * positive multiples of 8, for q8 vt_ld % 8 != 0, vt_ld < 8, vt_fs % vt_ld != 0 or vt_cols outside [1, vt_ld] (vt_ld / vt_cols are
+ * not read for native stores), k2 / vt2 / a store not 16-byte aligned, weights not 4-byte aligned — all before any launch.
+ * 16-byte vector stores on a grid-stride walk; no LDS, no atomics.
+ *
+ * aid_processor_kf_blend_fwd — aid_processor_corners_fwd whose corners are recorded key frames.  `args` describes the LOCAL frames
+ * only (the AID frames, then n_plain riders): a self-attention call (ctx == NULL, ip == NULL) with mode INNER or OUTER; args->coef /
+ * begin / end are not read.
+ *   OUTER  the workspace has M rows of k / V^T more than n_frames; one AID_KF_GET (aid_keyframe_rows or _q8, M rows) fills rows
+ *          n_frames + m from the stores, and the composition of aid_attn_corners_fwd runs with corner rows n_frames + m.
+ *   INNER  no extra rows: aid_mix_kv_stores writes the call's k2 / vt2, then the one aid_attn_fwd of the INNER composition runs
+ *          (coefficient 0.5 for every AID frame, -1 for the riders: no frame reads an end-point row).
+ * The workspace must hold aid_processor_kf_blend_workspace_bytes() bytes (0 for a call that would be refused).  b == NULL is
+ * aid_processor_fwd.  ctx != NULL, ip != NULL, mode == PLAIN and every AID_ERR_ARG / AID_ERR_SHAPE of AidKeyframeBlend above are
+ * refused with everything aid_processor_fwd checks, before the first launch.  LoRA / DoRA, LayerNorm (folded or not), residual,
+ * attn_bias (not with fused), f32_split / f32_attn_split and cu_share work as in aid_processor_fwd: it is the same code path.
+ * ------------------------------------------------------------------------------------- */
+typedef struct AidKeyframeBlend {
+    const AidKeyframeRow* rows;  /* HOST: n_corners entries (k_store, vt_store; `row` ignored) */
+    const int32_t*        step;  /* DEVICE                                                     */
+    const float*          weights; /* DEVICE fp32 [n_frames, n_corners], as AidCorners.weights */
+    int32_t n_corners;           /* 1 .. AID_MAX_CORNERS                                       */
+    int32_t n_steps;
+    int32_t q8;                  /* 0: native stores, 1: 8-bit block stores                    */
+} AidKeyframeBlend;
+
+int    aid_mix_kv_stores(const AidKeyframeBlend* b /* host */, void* k2, void* vt2, int32_t n_frames, int32_t n_plain, int64_t k_fs,
+                         int64_t vt_fs, int32_t vt_ld, int32_t vt_cols, int32_t dtype, void* stream);
+size_t aid_processor_kf_blend_workspace_bytes(const AidProcessorArgs* args /* host */, const AidKeyframeBlend* b /* host */);
+int    aid_processor_kf_blend_fwd(const AidProcessorArgs* args /* host */, const AidKeyframeBlend* b /* host */, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Live kernel timing (bench.py's roofline leg): between aid_profile_begin() and
  * aid_profile_end() every kernel launched through this library is bracketed by a pair of
  * HIP events recorded on the launch stream.  aid_profile_end() synchronises those events and
