@@ -788,6 +788,38 @@ class InterpolationStableDiffusionPipeline:
             self.unet.set_attn_processor(installed)
         return self._decode(lat, output_type)
 
+    # -- interpolate_save_gpu (gradio): the sequence bayesian_prior_selection scores ---------------------------------------------
+    @torch.no_grad()
+    def interpolate_save_gpu(self, latent_start: torch.Tensor, latent_end: torch.Tensor, prompt_start: Optional[str] = None,
+                             prompt_end: Optional[str] = None, guide_prompt: Optional[str] = None, negative_prompt: str = "",
+                             size: int = 7, num_inference_steps: int = 25, warmup_ratio: float = 0.5,
+                             early: str = "fused_outer", late: str = "self", alpha: Optional[float] = None,
+                             beta: Optional[float] = None, init: str = "linear", guidance_scale: Optional[float] = None,
+                             # build-specific
+                             endpoints: Optional[EndpointStore] = None, **kwargs):
+        """gradio_src/pipeline_interpolated_stable_diffusion.py:307-392: ``size`` frames at the coefficients
+        ``generate_beta_tensor(size, alpha, beta)`` (both default to ``num_inference_steps``), each interior frame rendered the way
+        ``interpolate_single(t_k)`` renders it.  The reference makes ``size - 2`` batch-3 runs, each denoising the two end points
+        again; here it is ONE ``interpolate(coef=[0, *t, 1])`` run — and with a recorded ``endpoints`` store a replay of the interior
+        frames alone.  Returns what ``interpolate`` returns (a numpy array of ``size`` frames for the default ``output_type``);
+        ``kwargs`` are ``interpolate``'s build-specific ones (``embeds_start``, ``output_type``, ``use_graphs``, ...).
+        ``init="denoising"`` (the reference's ``denoising_interpolate`` baseline) and the spherical embedding mix raise
+        ``NotImplementedError``."""
+        if init == "denoising":
+            raise NotImplementedError('init="denoising": the reference\'s denoising_interpolate baseline is not part of this package')
+        if init != "linear":
+            raise NotImplementedError(f"init={init!r}: the N-frame run mixes the text embeddings linearly (init=\"linear\")")
+        if alpha is None:
+            alpha = num_inference_steps
+        if beta is None:
+            beta = num_inference_steps
+        coef = [float(t) for t in generate_beta_tensor(size, alpha=alpha, beta=beta)]
+        coef[0], coef[-1] = 0.0, 1.0
+        return self.interpolate(latent_start, latent_end, prompt_start, prompt_end, guide_prompt=guide_prompt,
+                                negative_prompt=negative_prompt, size=size, num_inference_steps=num_inference_steps,
+                                warmup_ratio=warmup_ratio, early=early, late=late, guidance_scale=guidance_scale, coef=coef,
+                                endpoints=endpoints, **kwargs)
+
     # -- corner-weighted interpolation among up to eight end points (DESIGN.md §3.6f) ----------------------
     @torch.no_grad()
     def interpolate_corners(self, latents, prompts: Optional[Sequence[str]] = None, weights=None,

@@ -9,6 +9,9 @@ coefficient vector) — so it does not depend on diffusers / CLIP being importab
 filled per run instead of one batch-3 run per point.  With ``batch = 1`` the sequence of coefficients, distances and
 fitted parameters is the reference's (pinned against the reference in ``tests/test_prior.py``).
 
+``bayesian_prior_selection`` (prior.py:343-478) chooses the Beta prior itself: a Gaussian-process search over (alpha, beta) for the
+smoothest sequence, every evaluation a replay between end points recorded once.
+
 Host-side logic only (numpy / scipy); nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -19,6 +22,9 @@ import numpy as np
 import torch
 from scipy.optimize import curve_fit
 from scipy.stats import beta as beta_distribution
+
+from .interp import generate_beta_tensor
+from .metrics import adjacent_distances, compute_gini, compute_lpips, smoothness_and_consistency_of
 
 
 def clip_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -328,3 +334,279 @@ class BetaPriorPipeline:
         idxs = extract_uniform_points_plus(features, interpolation_size, self._compute_clip)
         self.images, self.ds, self.xs, self.alpha, self.beta_param = images, ds, xs, alpha, beta_param
         return [images[i] for i in idxs]
+
+
+# ---- automatic choice of the Beta prior (prior.py:343-478) --------------------------------------------------------------
+class GaussianProcessUCB:
+    """A small deterministic Gaussian-process / upper-confidence-bound maximiser over a box (numpy / scipy only) — the default
+    optimiser of ``bayesian_prior_selection``, where the reference uses ``bayes_opt.BayesianOptimization``.
+
+    ``register(point, score)`` adds an observation (duplicates allowed), ``suggest()`` returns the next point to evaluate: the
+    maximiser of ``mean + kappa * std`` of a zero-mean GP on the standardised scores, Matern-5/2 kernel over the unit box, over a
+    ``grid`` x ``grid`` set of candidates (one per cell, placed inside its cell by the generator ``random_state`` seeds).  The
+    kernel's length scale is the one of ``length_scales`` (fractions of the box; none shorter than a fifth of it — below the spacing of
+    the nine probes the mean falls back to the prior between observations and the search only explores) with the largest marginal
+    likelihood.  All state is the instance's own:
+    two instances with the same ``random_state`` fed the same observations propose the same points."""
+
+    def __init__(self, bounds: Sequence[Tuple[float, float]], random_state: int = 1, kappa: float = 2.576, grid: int = 49,
+                 length_scales: Sequence[float] = (0.2, 0.3, 0.5, 0.7, 1.0), jitter: float = 1e-6):
+        self.lo = np.array([float(b[0]) for b in bounds])
+        self.hi = np.array([float(b[1]) for b in bounds])
+        if np.any(self.hi < self.lo):
+            raise ValueError("bounds must be (low, high) pairs with low <= high")
+        self.kappa, self.grid, self.jitter = float(kappa), int(grid), float(jitter)
+        self.length_scales = tuple(float(l) for l in length_scales)
+        self._rng = np.random.RandomState(random_state)
+        self.points: List[Tuple[float, ...]] = []
+        self.scores: List[float] = []
+
+    def register(self, point: Sequence[float], score: float) -> None:
+        self.points.append(tuple(float(p) for p in point))
+        self.scores.append(float(score))
+
+    @property
+    def max(self) -> Tuple[Tuple[float, ...], float]:
+        """(point, score) of the best observation; the first of equals."""
+        i = int(np.argmax(self.scores))
+        return self.points[i], self.scores[i]
+
+    def _unit(self, x: np.ndarray) -> np.ndarray:
+        span = np.where(self.hi > self.lo, self.hi - self.lo, 1.0)
+        return (x - self.lo) / span
+
+    @staticmethod
+    def _matern52(a: np.ndarray, b: np.ndarray, length: float) -> np.ndarray:
+        r = np.sqrt(np.maximum(((a[:, None, :] - b[None, :, :]) ** 2).sum(-1), 0.0)) * (np.sqrt(5.0) / length)
+        return (1.0 + r + r * r / 3.0) * np.exp(-r)
+
+    def _candidates(self) -> np.ndarray:
+        """One candidate per cell of the grid over the unit box, at a seeded place inside its cell."""
+        g, dim = self.grid, len(self.lo)
+        cells = np.stack(np.meshgrid(*([np.arange(g)] * dim), indexing="ij"), -1).reshape(-1, dim)
+        return (cells + self._rng.uniform(size=cells.shape)) / g
+
+    def suggest(self) -> Tuple[float, ...]:
+        from scipy.linalg import cho_factor, cho_solve, solve_triangular
+        cand = self._candidates()
+        if not self.points:
+            u = cand[self._rng.randint(len(cand))]
+            return tuple(float(v) for v in self.lo + u * (self.hi - self.lo))
+        x = self._unit(np.asarray(self.points, dtype=np.float64))
+        y = np.asarray(self.scores, dtype=np.float64)
+        spread = y.std()
+        y = (y - y.mean()) / (spread if spread > 0 else 1.0)
+        best = None
+        for length in self.length_scales:
+            k = self._matern52(x, x, length) + self.jitter * np.eye(len(x))
+            fac = cho_factor(k, lower=True)
+            a = cho_solve(fac, y)
+            evidence = -0.5 * float(y @ a) - float(np.log(np.diag(fac[0])).sum())
+            if best is None or evidence > best[0]:
+                best = (evidence, length, fac, a)
+        _, length, fac, a = best
+        ks = self._matern52(cand, x, length)
+        mean = ks @ a
+        v = solve_triangular(fac[0], ks.T, lower=True)
+        std = np.sqrt(np.maximum(1.0 - (v * v).sum(0), 0.0))
+        u = cand[int(np.argmax(mean + self.kappa * std))]
+        return tuple(float(v_) for v_ in self.lo + u * (self.hi - self.lo))
+
+
+def _check_selection_init(init: str) -> None:
+    if init == "denoising":
+        raise NotImplementedError('init="denoising": the reference\'s denoising_interpolate baseline is not part of this package')
+    if init != "linear":
+        raise NotImplementedError(f"init={init!r}: the N-frame run mixes the text embeddings linearly (init=\"linear\")")
+
+
+_SELECTION_PIPE_KWARGS = ("embeds_start", "embeds_end", "embeds_guide", "output_type", "guidance_scale", "use_graphs",
+                          "cross_attention_kwargs", "init")
+
+
+class SmoothnessObjective:
+    """The black-box objective of ``bayesian_prior_selection`` (prior.py:387-416) and the run it stands on: ``prime()`` is the
+    ``interpolate_single(0.5)`` run that fixes the prior gate and ``init_smoothness``; ``__call__(alpha, beta)`` the gated score;
+    ``render(pairs)`` the frame sequences of several (alpha, beta) — one pipeline run per pair, or ONE replay run for all of them
+    (``batched=True``: the interior coefficients concatenated into one ``coef`` vector, each pair's frames sliced back out);
+    ``measure(frames)`` the triple (smoothness, consistency, maximum distance).
+
+    ``reuse_endpoints``: ``prime()`` records the two end points into an ``EndpointStore`` and every rendered sequence replays it —
+    only the ``size - 2`` interior frames go through the UNet, the end-point frames are the recorded ones."""
+
+    def __init__(self, pipe, latent1, latent2, prompt1, prompt2, lpips_model=None, guide_prompt=None, negative_prompt="",
+                 size: int = 3, num_inference_steps: int = 25, warmup_ratio: float = 1, early: str = "fused_outer",
+                 late: str = "self", distance: Optional[Callable] = None, reuse_endpoints: bool = True, **pipe_kwargs):
+        from .loop import EARLY_MODES
+        if early == "vfused":                # the reference's stale default (its own pipeline has no such mode): the pipelines' default
+            early = "fused_outer"
+        if early not in EARLY_MODES or (late != "self" and late not in EARLY_MODES):
+            raise ValueError(f"early / late must be in {EARLY_MODES} (late also 'self')")
+        unknown = sorted(set(pipe_kwargs) - set(_SELECTION_PIPE_KWARGS))
+        if unknown:
+            raise TypeError(f"unexpected keyword arguments {unknown}; the pipeline calls take {_SELECTION_PIPE_KWARGS}")
+        _check_selection_init(pipe_kwargs.get("init", "linear"))
+        if size < 3:
+            raise ValueError("size must be at least 3: two end points and an interior frame")
+        if distance is None and lpips_model is None:
+            raise ValueError("pass an `lpips_model`, or a `distance` for frames that are not images")
+        self.pipe, self.size, self.early, self.late = pipe, int(size), early, late
+        self.lpips_model, self.distance = lpips_model, distance
+        self.reuse_endpoints = bool(reuse_endpoints)
+        self.endpoints = None
+        self.init_smoothness = self.init_distances = self.large_alpha_prior = None
+        self.renders = 0                                 # pipeline runs made, the prime run included
+        self._common = dict(latent_start=latent1, latent_end=latent2, prompt_start=prompt1, prompt_end=prompt2,
+                            guide_prompt=guide_prompt, negative_prompt=negative_prompt,
+                            num_inference_steps=num_inference_steps, warmup_ratio=warmup_ratio, early=early, late=late,
+                            **pipe_kwargs)
+
+    # -- scoring ----------------------------------------------------------------------------------------------------------------
+    def distances(self, frames) -> np.ndarray:
+        if self.distance is not None:
+            return adjacent_distances(frames, self.distance)
+        return compute_lpips(frames, self.lpips_model)
+
+    def measure(self, frames) -> Tuple[float, float, float]:
+        return smoothness_and_consistency_of(self.distances(frames))
+
+    # -- rendering --------------------------------------------------------------------------------------------------------------
+    def prime(self):
+        """The ``t = 0.5`` run: neighbour distances of its three frames, ``init_smoothness``, and which side of alpha = beta the
+        prior allows.  With ``reuse_endpoints`` the run records the end points (a normal run, bit-identical outputs)."""
+        kw = dict(self._common)
+        installed = getattr(self.pipe, "_aid_early", None)
+        if installed is not None and (installed != self.early or self.late != "self"):
+            # this package's interpolate_single renders with the mode load_aid installed and plain attention afterwards
+            raise ValueError(f"the t = 0.5 run would render with the installed mode {installed!r} / 'self', the evaluations with "
+                             f"{self.early!r} / {self.late!r}: call load_aid(atype={self.early!r}) and keep late='self'")
+        if self.reuse_endpoints:
+            from .endpoint_store import EndpointStore
+            self.endpoints = EndpointStore()
+            kw["endpoints"] = self.endpoints
+        out = self.pipe.interpolate_single(it=0.5, **kw)
+        self.renders += 1
+        frames = out["images"] if isinstance(out, dict) else getattr(out, "images", out)
+        self.init_distances = self.distances(frames)
+        self.init_smoothness = 1 - compute_gini(self.init_distances)
+        self.large_alpha_prior = bool(self.init_distances[0] < self.init_distances[1])
+        return frames
+
+    def allowed(self, alpha: float, beta_param: float) -> bool:
+        """Does the prior let (alpha, beta) be rendered?  (alpha == beta is answered by ``init_smoothness``.)"""
+        return alpha > beta_param if self.large_alpha_prior else alpha < beta_param
+
+    def coefficients(self, alpha: float, beta_param: float) -> List[float]:
+        return [float(t) for t in generate_beta_tensor(self.size, alpha, beta_param)]
+
+    def render(self, pairs: Sequence[Tuple[float, float]], batched: bool = False) -> list:
+        """The ``size``-frame sequence of every (alpha, beta) of ``pairs``."""
+        pairs = list(pairs)
+        if self.reuse_endpoints and self.endpoints is None:
+            raise RuntimeError("render before prime(): the t = 0.5 run records the end points")
+        ep = {"endpoints": self.endpoints} if self.reuse_endpoints else {}
+        if not batched:
+            out = []
+            for a, b in pairs:
+                out.append(self.pipe.interpolate_save_gpu(size=self.size, alpha=a, beta=b, **self._common, **ep))
+                self.renders += 1
+            return out
+        if not self.reuse_endpoints:
+            raise ValueError("a batched render shares the recorded end points among its candidates: it needs reuse_endpoints")
+        if not pairs:
+            return []
+        k = self.size - 2
+        inner = [t for a, b in pairs for t in self.coefficients(a, b)[1:-1]]
+        kw = {n: v for n, v in self._common.items() if n != "init"}
+        frames = self.pipe.interpolate(size=len(inner) + 2, coef=[0.0] + inner + [1.0], **kw, **ep)
+        self.renders += 1
+        last = len(inner) + 1
+        return [frames[[0] + list(range(1 + j * k, 1 + (j + 1) * k)) + [last]] for j in range(len(pairs))]
+
+    def release(self) -> None:
+        """Drop the recorded end points."""
+        if self.endpoints is not None:
+            self.endpoints.clear()
+            self.endpoints = None
+
+    def __call__(self, alpha: float, beta_param: float, frames=None) -> Tuple[float, bool]:
+        """(score, rendered) of one (alpha, beta): 0 on the side the prior refuses and ``init_smoothness`` on the diagonal, both
+        without rendering; else the smoothness of the rendered sequence (``frames``: already rendered by a batched run)."""
+        if alpha == beta_param:
+            return self.init_smoothness, False
+        if not self.allowed(alpha, beta_param):
+            return 0, False
+        if frames is None:
+            frames = self.render([(alpha, beta_param)])[0]
+        return self.measure(frames)[0], True
+
+
+def bayesian_prior_selection(interpolation_pipe, latent1, latent2, prompt1, prompt2, lpips_model, guide_prompt=None,
+                             negative_prompt="", size=3, num_inference_steps=25, warmup_ratio=1, early="vfused", late="self",
+                             target_score=0.9, n_iter=15, p_min=None, p_max=None, *, distance: Optional[Callable] = None,
+                             reuse_endpoints: bool = True, batch_probes: bool = True, optimizer=None,
+                             return_trace: bool = False, **pipe_kwargs):
+    """Choose the Beta prior (alpha, beta) of an interpolation by maximising the smoothness ``1 - gini`` of the perceptual
+    distances between neighbouring frames (prior.py:343-478): same positional signature, defaults and decision structure.
+
+    One ``interpolate_single(0.5)`` run gives the prior — alpha > beta when the middle frame is nearer the first end point — and
+    the score of every alpha == beta.  The 3 x 3 grid ``{p_min, (p_min + p_max) / 2, p_max}^2`` is probed alpha-major and the FIRST
+    probe that reaches ``target_score`` is returned; then at most ``n_iter`` proposals of the optimiser follow, one at a time, until
+    the best score reaches the target; the best point evaluated is returned.  ``p_min = 1``, ``p_max = warmup_ratio *
+    num_inference_steps`` unless given.  ``early="vfused"`` (the reference's stale default) means ``"fused_outer"``.
+
+    Build-specific, keyword-only: ``distance(frame_a, frame_b)`` scores frames that are not images (then ``lpips_model`` may be
+    None).  ``reuse_endpoints``: the first run records the two end points (``EndpointStore``), every rendered evaluation replays them
+    — ``size - 2`` frames through the UNet instead of ``size``; ``False`` renders every evaluation in full.  ``batch_probes``: the
+    probes that need rendering share ONE replay run, made before the scan (which still reads the scores in the reference's order);
+    needs ``reuse_endpoints``.  ``optimizer``: an object with ``suggest() -> (alpha, beta)`` and ``register((alpha, beta), score)``
+    (default :class:`GaussianProcessUCB`, ``random_state=1``).  ``return_trace``: also return the list of ``(alpha, beta, score,
+    rendered)`` in evaluation order.  ``pipe_kwargs`` (``embeds_start``, ``embeds_end``, ``embeds_guide``, ``output_type``,
+    ``guidance_scale``, ``use_graphs``, ``cross_attention_kwargs``) reach the pipeline calls unchanged."""
+    if batch_probes and not reuse_endpoints:
+        raise ValueError("batch_probes renders the probes in one replay run between the recorded end points: it needs "
+                         "reuse_endpoints=True")
+    objective = SmoothnessObjective(interpolation_pipe, latent1, latent2, prompt1, prompt2, lpips_model, guide_prompt=guide_prompt,
+                                    negative_prompt=negative_prompt, size=size, num_inference_steps=num_inference_steps,
+                                    warmup_ratio=warmup_ratio, early=early, late=late, distance=distance,
+                                    reuse_endpoints=reuse_endpoints, **pipe_kwargs)
+    trace: List[Tuple[float, float, float, bool]] = []
+
+    def result(alpha, beta_param):
+        return ((alpha, beta_param), trace) if return_trace else (alpha, beta_param)
+
+    try:
+        objective.prime()
+        if p_min is None:
+            p_min = 1
+        if p_max is None:
+            p_max = warmup_ratio * num_inference_steps
+        if optimizer is None:
+            optimizer = GaussianProcessUCB(((p_min, p_max), (p_min, p_max)), random_state=1)
+
+        def evaluate(alpha, beta_param, frames=None):
+            score, rendered = objective(alpha, beta_param, frames)
+            trace.append((alpha, beta_param, score, rendered))
+            optimizer.register((alpha, beta_param), score)
+            return score
+
+        axis = [p_min, (p_min + p_max) / 2, p_max]
+        probes = [(a, b) for a in axis for b in axis]                    # alpha-major (prior.py:459-460)
+        ready = {}
+        # (the first probe is the diagonal point (p_min, p_min): when init_smoothness already reaches the target the scan ends there and,
+        # as in the reference, nothing is rendered)
+        if batch_probes and not objective.init_smoothness >= target_score:
+            need = [p for p in dict.fromkeys(probes) if p[0] != p[1] and objective.allowed(*p)]
+            ready = dict(zip(need, objective.render(need, batched=True)))
+        for alpha, beta_param in probes:
+            if evaluate(alpha, beta_param, ready.get((alpha, beta_param))) >= target_score:
+                return result(alpha, beta_param)
+        for _ in range(n_iter):
+            alpha, beta_param = optimizer.suggest()
+            evaluate(alpha, beta_param)
+            if max(s for _, _, s, _ in trace) >= target_score:
+                break
+        alpha, beta_param, _, _ = max(trace, key=lambda e: e[2])         # the first of equals, like ``optimizer.max``
+        return result(alpha, beta_param)
+    finally:
+        objective.release()
